@@ -6,7 +6,7 @@
 Default (`--mode wsi`): the whole `run_infer_wsi.py` job on ONE synthetic 40000 x 40000 x 3 slide (BASELINE.json north_star /
 configs[2-3]; 24,649 tiles of 256 x 256) resident in HBM, sharded over the N ranks by contiguous bands of patch rows (STRONG
 scaling: the slide is fixed, every rank owns 1/N of it):
-    timed region = K steps, step k = stripe k of this rank's band: on-device patch gather -> forward of all six heads -> fused
+    timed region = K steps, every step the whole job: this rank's band in STRIPES stripes of on-device patch gather -> forward of all six heads -> fused
                    softmax / crop / argmax -> scatter into the band's canvases (cerberus_amd.wsi.WSIRunner.infer_patches),
                  + the slide's tail: halo exchange with the neighbouring ranks (RCCL send/recv over xGMI), on-GPU labelling of the
                    band (nuclei at full resolution, gland / lumen at x0.5, lumen-in-gland masking), instance tables, slide-global
@@ -14,16 +14,20 @@ scaling: the slide is fixed, every rank owns 1/N of it):
                    (cerberus_amd.shard_postproc.postprocess_bands_and_gather -- the function run_infer_wsi.py calls).
 A random-weight network paints slide-sized blobs, so the labelling leg reads seeded STRUCTURED probability maps of the slide's
 size instead (600 nuclei / Mpx of radius 4-9 px, glands of 25-150 px; SURVEY.md par.8d cfg 3): same kernels, same band
-protocol, realistic instance counts (~1 M nuclei).  `value` = slide pixels / wall time of that whole region (max over ranks);
-`config.inference_Mpx_s` is the same slide over the K inference steps alone.
+protocol, realistic instance counts (~1 M nuclei).  `value` = K x slide pixels / wall time of that whole region (max over ranks), i.e.
+slide pixels per second of one job; `ms_per_step` = milliseconds of one job; `config.inference_Mpx_s` is the same slide over the inference alone.
+The W warm-up steps are whole jobs too, run untimed after the set-up.
 `--mode batch`: the inner loop alone on 32 resident tiles (BASELINE.json configs[1]); `--mode train`: configs[4]; `--mode ingest`: a JPEG-tiled
 pyramidal TIFF on disk through reader -> decode pool -> upload-ahead -> inference, beside the resident figure (`--ingest-codec deflate | lzw`: lossless
 tiles through libcerberus_host.so's one-call-per-window reader; `--ingest-base-mpp 0.25`: a 40x scan reduced on the device).
-Beside `value` the default line carries (all outside the timed region): `config.conv_algo` / `config.precision` (the 3x3 algorithm the headline ran on, the
-calibration measurement, what the head kernels' max-|logit| guard saw over the job's batches), `config.other_conv_algos` (the same slide's inference on
+A plain run of the default mode sets up, warms up, times the K steps and prints the line; beside `value` it carries what the timed job itself
+reports: `config.conv_algo` / `config.precision` (the 3x3 algorithm the headline ran on, the calibration measurement, what the head kernels'
+max-|logit| guard saw over the job's batches), `postproc`, `multi_gpu`.  `--dump-outputs DIR`: after the timed steps, a fixed seeded sample of
+what the timed job returned (label maps, class maps, the inference's INST probability canvases) as DIR/<name>.npy in float32 / float64.
+With `--full` the default line also carries (all outside the timed region): `config.other_conv_algos` (the same slide's inference on
 F(2x2) and on the direct kernels), `dat` (instance tables + contours + the .dat writer; with several ranks `dat.per_rank_arrays`: tables + contours where
 the instances live, compact arrays gathered, bytes into rank 0 either way), `ref_tiling`, `ingest` (a 12288^2 JPEG-tiled TIFF; `ingest_40x`: stored at 0.25 mpp; `ingest_deflate`: lossless tiles through the native reader), `batch_step`, `train_step`,
-`dice_vs_reference`, `cpu_baseline`.  `--tail-from-inference`: the tail labels the canvases the timed inference wrote.
+`dice_vs_reference`, `cpu_baseline`, `roofline`, `kernels`.  `--tail-from-inference`: the tail labels the canvases the timed inference wrote.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -40,9 +44,31 @@ import torch  # noqa: E402
 
 BATCH, TILE = 32, 256
 WSI_BATCH = int(os.environ.get("CERB_WSI_BATCH", "0"))  # tiles per forward of the slide job; 0 = 64 with two streams (152.4 Mpx/s; 96: 151.9, 48: 150.6), 96 with one (149.9)
+STRIPES = 20  # pieces one slide job queues its patches in (batch-aligned): the stripe length of the default line before a step became a whole job
 MARGIN = 1024  # halo rows exchanged between neighbouring bands (full resolution): above the tallest gland cluster of the structured maps
 MARGINS = {"Nuclei": 128, "Gland": MARGIN, "Lumen": 512}  # per tissue: nuclei are < 30 px (the reference's own tile margin is 64)
 PEAK_F32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
+
+
+def _host_cpus():
+    """CPUs this process may keep busy: the affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS when either is set (a shared
+    host's affinity mask can list every core while the job's share is far smaller; sweeping threads or processes past that share times
+    the scheduler's throttling, not the decoder or the CPU forward)."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) / int(period))))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def _cpu_forward_rate(sd, kw, threads, n_tiles, iters, budget_s):
@@ -73,10 +99,7 @@ def cpu_baseline(sd, kw, n_tiles=8, iters=1):
     threads 0.0009 Mpx/s -- the warm-up tile alone took 70 s), so the thread count is SWEPT (16 / 32 / 64 / 128, each on the same bounded
     sample, ~5 s apiece) and the best one is reported as `value` with its `cores`; `sweep` carries every point, `all_cores` the whole-host figure
     when the sweep has not already collapsed below half of its best by 128 threads."""
-    try:
-        avail = len(os.sched_getaffinity(0))
-    except AttributeError:
-        avail = os.cpu_count() or 1
+    avail = _host_cpus()
     cand = sorted(set(min(avail, c) for c in (16, 32, 64, 128)))
     sweep, best = [], None
     for c in cand:
@@ -124,10 +147,7 @@ def cpu_baseline_train(sd, kw):
     BOUNDED sample -- 2 tiles of 448 x 448 (BatchNorm in training mode needs more than one sample), one warm-up step + one timed."""
     from oracle import train_step_ref
 
-    try:
-        avail = len(os.sched_getaffinity(0))
-    except AttributeError:
-        avail = os.cpu_count() or 1
+    avail = _host_cpus()
     cores = min(avail, 16)
     torch.set_num_threads(cores)
     heads = {"Lumen-INST": 3, "Gland-INST": 3, "Nuclei-INST": 3, "Nuclei-TYPE": 7, "Gland-TYPE": 3, "Patch-Class": 9}
@@ -491,6 +511,27 @@ def batch_loop(model, dev, rank, steps, warmup, dist, backend):
     return dt, step, BATCH
 
 
+DUMP_SAMPLE = 1 << 19  # elements kept per dumped array: the default mode's 9 arrays stay near 30 MB, under the 64 MB bound
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """arrays: name -> tensor / ndarray.  Each is written as outdir/<name>.npy, flattened: whole when it holds at most DUMP_SAMPLE elements,
+    otherwise the elements at up to DUMP_SAMPLE row-major positions drawn from RandomState(seed) -- the same positions for the same shape, run
+    after run (gathered where the array lives, without copying a strided view whole).  Floating arrays as float32, integer ones (label ids,
+    classes) as float64, which holds every int32 exactly."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, v in arrays.items():
+        t = v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v))
+        n = int(np.prod(t.shape))
+        if n > DUMP_SAMPLE:
+            idx = np.unique(np.random.RandomState(seed).randint(0, n, DUMP_SAMPLE, dtype=np.int64))
+            flat = t[tuple(torch.from_numpy(c).to(t.device) for c in np.unravel_index(idx, tuple(t.shape)))]
+        else:
+            flat = t.reshape(-1)
+        a = flat.cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+        np.save(os.path.join(outdir, name.replace("/", "_").replace("@", "_at_") + ".npy"), a)
+
+
 def _timed(fn, dev, dist, backend):
     """barrier + synchronize on both sides, max over ranks"""
     torch.cuda.synchronize()
@@ -607,10 +648,7 @@ def ingest_leg(model, dev, side, batch, streams, tmpdir=None, sweep=(1, 2, 4, 8,
         span = min(fH, 2048)
         old = os.environ.get("CERB_DECODE_THREADS")
         old_procs = os.environ.get("CERB_DECODE_PROCS")
-        try:
-            avail = len(os.sched_getaffinity(0))
-        except AttributeError:
-            avail = os.cpu_count() or 1
+        avail = _host_cpus()
         dec = []
         os.environ["CERB_DECODE_PROCS"] = "0"
         reader._read_level(0, 0, 0, fW, span)
@@ -781,12 +819,13 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
         struct = OrderedDict((k, v[:valid, :W]) for k, v in run.canv.items() if k.endswith("INST"))
     else:
         struct = structured_band(dev, run.r0 * TILE, valid, W)
-    # stripes: this rank's patches in K contiguous pieces, cut at batch boundaries
+    # stripes: one job queues this rank's patches in S contiguous pieces, cut at batch boundaries (S = STRIPES, fewer on a band of fewer batches)
     nb = -(-run.n_patches // WSI_BATCH)
-    cuts = [min(run.n_patches, c * WSI_BATCH) for c in band_partition(nb, K)]
+    S = max(1, min(STRIPES, nb))
+    cuts = [min(run.n_patches, c * WSI_BATCH) for c in band_partition(nb, S)]
     max_band_px = int(args.max_band_mpx * 1e6)
     # warm-up: W stripes' worth of batches + one small labelling call per tissue (allocations, code objects, RCCL channels)
-    for k in range(min(args.warmup, K)):
+    for k in range(min(args.warmup, S)):
         run.infer_patches(slab, y0, cuts[k], min(cuts[k] + 2 * WSI_BATCH, cuts[k + 1]))
     from cerberus_amd.postproc import _workspace, postproc_device
 
@@ -802,7 +841,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
         need = 0.7e9 * WSI_BATCH + 0.04e9 * (valid * W / 1e6) * 1e0 + 8e9
         if torch.cuda.mem_get_info(dev)[0] > need:
             run.twin = model.twin()
-            for k in range(min(max(args.warmup, 1), K)):
+            for k in range(min(max(args.warmup, 1), S)):
                 _warm_handles(run, slab, y0, cuts[k], min(cuts[k] + 2 * WSI_BATCH, cuts[-1]))
             torch.cuda.synchronize()
         else:
@@ -825,8 +864,11 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
     res = {}
 
     def job():
+        """One step: the whole slide job.  prof / res then hold this job's figures and outputs; phase sums the seconds of every job run."""
         from cerberus_amd.shard_postproc import band_view, make_incremental
 
+        prof.clear()
+        res.clear()
         t0 = time.perf_counter()
         canv = OrderedDict(struct)
         # One GPU, several local labelling bands: a band is labelled on a side stream as soon as the stripes that cover its rows and its halo have
@@ -835,7 +877,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
         # finished its rows, and is only started after the NEXT stripe has been queued (the host then has a stripe of device work ahead of it).
         pre = make_incremental(band_view(run, H, W, canv), dist, margin=MARGINS, guard=48, max_band_px=max_band_px) if args.overlap_tail else {}
         evs = []
-        for k in range(K):
+        for k in range(S):
             # (no join of the two handles' streams between the stripes unless the overlapped labelling needs a per-stripe completion event)
             run.infer_patches(slab, y0, cuts[k], cuts[k + 1], join=bool(pre))
             if pre:
@@ -847,22 +889,29 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
                         lab.feed(run.rows_final(cuts[k]), [evs[k - 1]])
         run.join()
         torch.cuda.synchronize()
-        phase["inference_s"] = time.perf_counter() - t0
+        phase["inference_s"] = phase.get("inference_s", 0.0) + time.perf_counter() - t0
         t1 = time.perf_counter()
         inst, info, small = postprocess_bands_and_gather(run, H, W, rank, world, dist, margin=MARGINS, guard=48, canv=canv, max_band_px=max_band_px,
                                                          prof=prof, watch=args.watch, pre=pre)
         torch.cuda.synchronize()
-        phase["tail_s"] = time.perf_counter() - t1
+        phase["tail_s"] = phase.get("tail_s", 0.0) + time.perf_counter() - t1
         res.update(inst=inst, info=info, small=small)
 
     if os.environ.get("CERB_BENCH_PROBE_REPEAT"):  # developer probe: is the first full-size tail slower than the second (allocator warm-up)?
         for _ in range(int(os.environ["CERB_BENCH_PROBE_REPEAT"])):
+            phase.clear()
             dtp = _timed(job, dev, dist, args.backend)
             print("probe: job %.3f s inference %.3f tail %.3f nuclei %.3f" % (dtp, phase["inference_s"], phase["tail_s"], prof.get("label_Nuclei", {}).get("s", -1)),
                   file=sys.stderr, flush=True)
-            prof.clear()
-            res.clear()
-    dt = _timed(job, dev, dist, args.backend)
+    # W warm-up steps: whole jobs like the timed ones, untimed
+    for _ in range(args.warmup):
+        job()
+    torch.cuda.synchronize()
+    # the timed region: K steps = K whole jobs of the same slide; `value` = slide pixels / seconds per job
+    phase.clear()
+    dt = _timed(lambda: [job() for _ in range(K)], dev, dist, args.backend)
+    for key in ("inference_s", "tail_s"):  # seconds per job
+        phase[key] /= K
     if dist is not None:  # slowest rank's phases
         for key in ("inference_s", "tail_s"):
             t = torch.tensor([phase[key]], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -878,6 +927,11 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
     if small_sum is not None and world == 1:  # one rank: the gathered class maps ARE the inference's canvases, cropped to the slide
         for k, v in small_sum.items():
             assert v == _csum(run.canv[k][:valid, :W]), "the tail's %s map is not the inference's canvas" % k
+    if args.dump_outputs and rank == 0:
+        outs = OrderedDict(("labels_" + t, v) for t, v in (res.get("inst") or {}).items())
+        outs.update(("classes_" + k, v) for k, v in (res.get("small") or {}).items())
+        outs.update(("canvas_" + k, v[:valid, :W]) for k, v in run.canv.items() if k.endswith("INST"))  # (rank 0's band)
+        dump_outputs(args.dump_outputs, outs)
     n_inst = {t: int(i.get("n_total", 0)) for t, i in info.items()}
     checks = {t: {"n_truncated": int(i.get("n_truncated", 0)), "n_unresolved": int(i.get("n_unresolved", 0)), "local_bands": int(i.get("local_bands", 1)),
                   "bands_labelled_under_inference": int(i.get("bands_labelled_under_inference", 0))}
@@ -886,7 +940,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
     # joblib.dump): contour tracing on the GPU (cerb_inst_contour_*), the per-instance dictionaries on the host, and the .dat file.  Timed here,
     # AFTER the headline region (the metric counts pixels inferred and labelled; `end_to_end_Mpx_s` = the same slide over job + dictionary + file).
     dat = None
-    if rank == 0 and not args.no_dat:
+    if rank == 0 and args.full and not args.no_dat:
         import tempfile
 
         from cerberus_amd.wsi import DatWriter, collect_wsi_inst_arrays, wsi_meta
@@ -905,7 +959,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
             pth = os.path.join(td, "slide.dat")
             wr = DatWriter.from_arrays(parts, wsi_meta((H, W), 0.5), pth)
             t2 = time.perf_counter()
-            for k in range(K):
+            for k in range(S):
                 run.infer_patches(slab, y0, cuts[k], cuts[k + 1])
             torch.cuda.synchronize()
             t3 = time.perf_counter()
@@ -928,7 +982,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
     # label bands and class canvases (15 B/px) stay on their ranks.  The whole tail again with that hand-over, untimed by `value` (which keeps the
     # map stitch north_star names): seconds of the per-rank tables + contours (slowest rank), bytes into the root either way.
     per_rank = None
-    if dist is not None and not args.no_dat:
+    if dist is not None and args.full and not args.no_dat:
         parts2, prof2 = [], {}
 
         def arr_job():
@@ -955,7 +1009,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
     # tile labelled with skimage's tie order), tiles sharded over the ranks (cerberus_amd/ref_tiling.py) -- what `run_infer_wsi.py
     # --reference_tiling` runs instead of the band scheme.  `value` uses the band scheme; this leg is timed beside it.
     rt = None
-    if not args.no_ref_tiling:
+    if args.full and not args.no_ref_tiling:
         from cerberus_amd.ref_tiling import reference_tiled_nuclei_sharded
 
         tprof = {}
@@ -975,46 +1029,48 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
                           "the reference's own tile sets, no Python object per instance; compare with dat.tables_and_contours_s + postproc.Nuclei.s of the "
                           "band scheme"}
         res.clear()
-    # secondary: the inner loop alone (configs[1]) + the per-kernel table of one batch step
-    bdt, bstep, bn = batch_loop(model, dev, rank, 20, 3, None, args.backend)
-    roofline, rows = kernel_table(model, bstep, bn)
+    # secondary (--full): the inner loop alone (configs[1]) + the per-kernel table of one batch step
+    if args.full:
+        bdt, bstep, bn = batch_loop(model, dev, rank, 20, 3, None, args.backend)
+        roofline, rows = kernel_table(model, bstep, bn)
     # what the head kernels saw during the timed job (cerb_forward_io.logit_absmax, one row per batch) and the algorithm the headline ran on
     guard = run.logit_report()
     precision = dict(model.precision_decision(), name=CONV_ALGO_NAMES.get(model.precision_decision()["conv_algo"]),
                      logit_saturation=model.LOGIT_SATURATION,
                      logit_guard={"batches": guard["batches"], "batches_above": guard["above"], "largest_abs_logit": round(guard["max"], 3)})
-    # The headline's precondition made explicit: the same slide's inference on the algorithms a model that trips the
-    # calibration probe (conv_algo 1) or a caller's explicit choice (0) would run -- 4 of the K stripes each, same runner, same handles, same
+    # (--full) The headline's precondition made explicit: the same slide's inference on the algorithms a model that trips the
+    # calibration probe (conv_algo 1) or a caller's explicit choice (0) would run -- 4 of a job's S stripes each, same runner, same handles, same
     # streams, barrier + synchronize on both sides; `value_with_default_tail` = slide pixels / (that inference rate over the whole slide + the
     # default run's measured tail): an estimate built from two measurements, said so.
     algo_values = {}
-    try:
-        ks = min(4, K)
-        for algo in (1, 0):
+    if args.full:
+        try:
+            ks = min(4, S)
+            for algo in (1, 0):
+                for h in (model, run.twin):
+                    if h is not None:
+                        h.set_conv_algo(algo)
+                _warm_handles(run, slab, y0, cuts[0], min(cuts[0] + 2 * WSI_BATCH, cuts[-1]))  # warm-up (workspaces of this algorithm, on BOTH handles)
+                torch.cuda.synchronize()
+
+                def part():
+                    for k in range(ks):
+                        run.infer_patches(slab, y0, cuts[k], cuts[k + 1], join=False)
+                    run.join()
+
+                adt = _timed(part, dev, dist, args.backend)
+                apx = (cuts[ks] - cuts[0]) * TILE * TILE * world  # (every rank runs the same number of its own patches, up to one batch)
+                abdt, _, _ = batch_loop(model, dev, rank, 4, 1, None, args.backend)
+                inf_s = px_all(H, W) / (apx / adt)
+                algo_values[str(algo)] = {"name": CONV_ALGO_NAMES[algo], "stripes": ks, "inference_Mpx_s": round(apx / adt / 1e6, 3),
+                                          "value_with_default_tail": round(px_all(H, W) / (inf_s + phase["tail_s"]) / 1e6, 3),
+                                          "batch_step_ms": round(abdt / 4 * 1e3, 3)}
+        except Exception as e:  # never fails the headline
+            algo_values["error"] = str(e)[:300]
+        finally:
             for h in (model, run.twin):
                 if h is not None:
-                    h.set_conv_algo(algo)
-            _warm_handles(run, slab, y0, cuts[0], min(cuts[0] + 2 * WSI_BATCH, cuts[-1]))  # warm-up (workspaces of this algorithm, on BOTH handles)
-            torch.cuda.synchronize()
-
-            def part():
-                for k in range(ks):
-                    run.infer_patches(slab, y0, cuts[k], cuts[k + 1], join=False)
-                run.join()
-
-            adt = _timed(part, dev, dist, args.backend)
-            apx = (cuts[ks] - cuts[0]) * TILE * TILE * world  # (every rank runs the same number of its own patches, up to one batch)
-            abdt, _, _ = batch_loop(model, dev, rank, 4, 1, None, args.backend)
-            inf_s = px_all(H, W) / (apx / adt)
-            algo_values[str(algo)] = {"name": CONV_ALGO_NAMES[algo], "stripes": ks, "inference_Mpx_s": round(apx / adt / 1e6, 3),
-                                      "value_with_default_tail": round(px_all(H, W) / (inf_s + phase["tail_s"]) / 1e6, 3),
-                                      "batch_step_ms": round(abdt / 4 * 1e3, 3)}
-    except Exception as e:  # never fails the headline
-        algo_values["error"] = str(e)[:300]
-    finally:
-        for h in (model, run.twin):
-            if h is not None:
-                h.set_conv_algo(6)
+                    h.set_conv_algo(6)
     if rank != 0:
         return
     px = H * W
@@ -1043,7 +1099,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
             mg["root_gather"]["GB_s_per_link"] = round(mg["root_gather"]["GB_s"] / max(1, world - 1), 2)
     line = {
         "metric": "Mpx/sec WSI tiled inference (all heads)",
-        "value": round(px / dt / 1e6, 3),
+        "value": round(px * K / dt / 1e6, 3),
         "unit": "Mpx/s",
         "n_gpus": world,
         "steps": K,
@@ -1058,38 +1114,42 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
             "workload": "Synthetic %dx%dx3 uint8 WSI resident in HBM (BASELINE.json north_star / configs[%d]), sliding window 256-in / 256-out = %d tiles, "
                         "full Cerberus (ResNet34 + 6 heads, fp32) with on-device patch gather + canvas scatter, then on-GPU post-processing of "
                         "slide-sized structured maps (nuclei watershed at x1, gland / lumen at x0.5, instance tables, global ids) and the label "
-                        "stitch on rank 0; a step = 1/%d of every rank's band, the tail is inside the timed region" % (H, W, 3 if side >= 40000 else 2, n_tiles, K),
+                        "stitch on rank 0; a step = the whole job (every rank's band in %d stripes, then the tail), %d steps timed" % (H, W, 3 if side >= 40000 else 2, n_tiles, S, K),
             "slide": [H, W],
             "tiles": n_tiles,
             "batch_tiles": WSI_BATCH, "streams": args.streams, "overlap_tail": int(bool(args.overlap_tail and dist is None)),
-            "conv_algo": precision["conv_algo"], "precision": precision, "other_conv_algos": algo_values,
+            "conv_algo": precision["conv_algo"], "precision": precision,
             "inference_s": round(phase["inference_s"], 3),
             "inference_Mpx_s": round(px / phase["inference_s"] / 1e6, 3),
             "postproc_and_stitch_s": round(phase["tail_s"], 3),
-            "whole_job_s": round(dt, 3),
+            "whole_job_s": round(dt / K, 3),
             "tail_inputs": {"INST probability maps": ("the canvases this job's timed inference wrote (--tail-from-inference: the seeded weights with the INST heads' "
                                                       "background bias raised so that ~3 %% of the pixels are foreground; shifts %s)" % fg_shifts) if args.tail_from_inference else
                                                      "seeded structured maps of the slide's size (random weights make no instances; cerberus_amd/synth_maps.py)",
                             "TYPE and Patch-Class maps": "the canvases this job's inference wrote (majority types of the instance tables, class-map gather)",
                             "class_canvas_checksum": small_sum},
             "nuclei_scheme": "exact band ownership (every instance of the whole-slide labelling once; cerberus_amd/shard_postproc.py) -- the reference's own "
-                             "4096-px tile sets + 64-px margins (`run_infer_wsi.py --reference_tiling`) are timed beside it as `ref_tiling`",
+                             "4096-px tile sets + 64-px margins (`run_infer_wsi.py --reference_tiling`) are timed beside it as `ref_tiling` (--full)",
             "inference_algorithmic_tflops_per_gpu": round(n_tiles * flops_tile / phase["inference_s"] / 1e12 / world, 2),
             "gflop_per_tile": round(flops_tile / 1e9, 3),
             "parallelism": "band-sharded x%d (contiguous patch rows), no collective during inference; halo send/recv + 2 all-gathers + 1 gather per "
                            "label map in the tail (%s)" % (world, args.backend if world > 1 else "single GPU"),
         },
-        "roofline": roofline,
-        "kernels": rows,
         "postproc": pp,
-        "dat": dat if dat is not None else ({"per_rank_arrays": per_rank} if per_rank else None),
-        "ref_tiling": rt,
-        "end_to_end_Mpx_s": round(px / (dt + dat["dat_s"]) / 1e6, 3) if dat else None,
         "multi_gpu": mg,
-        "batch_step": {"workload": "configs[1]: batch=32 256x256 tiles, inner loop only", "ms_per_step": round(bdt / 20 * 1e3, 3),
-                       "Mpx_s": round(20 * BATCH * TILE * TILE / bdt / 1e6, 2)},
     }
-    if world == 1 and not args.no_train_leg:
+    if args.full:
+        line["config"]["other_conv_algos"] = algo_values
+        line.update({
+            "roofline": roofline,
+            "kernels": rows,
+            "dat": dat if dat is not None else ({"per_rank_arrays": per_rank} if per_rank else None),
+            "ref_tiling": rt,
+            "end_to_end_Mpx_s": round(px / (dt / K + dat["dat_s"]) / 1e6, 3) if dat else None,
+            "batch_step": {"workload": "configs[1]: batch=32 256x256 tiles, inner loop only", "ms_per_step": round(bdt / 20 * 1e3, 3),
+                           "Mpx_s": round(20 * BATCH * TILE * TILE / bdt / 1e6, 2)},
+        })
+    if world == 1 and args.full and not args.no_train_leg:
         # BASELINE.json configs[4] rides along in the default line (3 steps, batch 16 x 448 x 448 on this GPU; `--mode train` is the full leg):
         # the slide job's buffers are released first, the training handle is a second, train-packed copy of the same weights
         try:
@@ -1107,7 +1167,7 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
             del tm
         except Exception as e:  # never fails the headline
             line["train_step"] = {"error": str(e)[:300]}
-    if world == 1 and not args.no_ingest_leg:
+    if world == 1 and args.full and not args.no_ingest_leg:
         # a slide on DISK (JPEG-tiled pyramidal TIFF) through the reader / decode pool / upload-ahead path, beside the resident figure (`--mode ingest`: 20000^2)
         try:
             line["ingest"] = ingest_leg(model, dev, 12288, WSI_BATCH, 1)
@@ -1125,12 +1185,12 @@ def wsi_leg(args, model, dev, dist, world, rank, sd, kw):
             line["ingest_deflate"] = {k: ingd[k] for k in ("slide", "file", "decode", "inference_resident", "end_to_end_from_file", "best")}
         except Exception as e:  # never fails the headline
             line["ingest_deflate"] = {"error": str(e)[:300]}
-    if world == 1:  # per-head Dice against the reference's own outputs (the metric's second half), outside the timed region
+    if world == 1 and args.full:  # per-head Dice against the reference's own outputs (the metric's second half), outside the timed region
         try:
             line["dice_vs_reference"] = dice_vs_reference()
         except Exception as e:  # never fails the headline
             line["dice_vs_reference"] = {"error": str(e)[:300]}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(sd, kw)
     print(json.dumps(line), flush=True)
 
@@ -1140,11 +1200,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="default mode: also run and report every leg beside the headline (other 3x3 algorithms, dat, ref_tiling, batch_step + per-kernel "
+                         "roofline, train_step, ingest, dice_vs_reference, cpu_baseline); the --no-* switches below then drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default mode: after the timed steps, write a fixed seeded sample of what the timed job returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dat", action="store_true", help="skip the untimed-by-`value` instance-dictionary leg (`dat`: contours + dictionary + .dat file)")
     ap.add_argument("--no-ref-tiling", action="store_true", help="skip the `ref_tiling` leg (the reference's own nuclei tile scheme over the same maps)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the short configs[4] training leg that the default (wsi, 1 GPU) line carries as `train_step`")
-    ap.add_argument("--no-ingest-leg", action="store_true", help="skip the `ingest` leg of the default line (a 12288^2 JPEG-tiled TIFF through reader -> decode pool -> upload-ahead -> inference)")
+    ap.add_argument("--no-train-leg", action="store_true", help="skip the short configs[4] training leg that the default (wsi, 1 GPU) --full line carries as `train_step`")
+    ap.add_argument("--no-ingest-leg", action="store_true", help="skip the `ingest` leg of the default --full line (a 12288^2 JPEG-tiled TIFF through reader -> decode pool -> upload-ahead -> inference)")
     ap.add_argument("--mode", default="wsi", choices=["wsi", "batch", "infer", "train", "ingest"],
                     help='"wsi" (default): the headline, whole-slide job of north_star / configs[2-3]; "batch" (= "infer"): configs[1] inner loop; '
                          '"train": the multi-task training step of configs[4]')
@@ -1173,6 +1238,8 @@ def main():
                     help="with --backend gloo only: let the N self-spawned ranks time-share fewer than N devices (plumbing tests on a one-GPU box); "
                          "RCCL needs one device per rank and never oversubscribes")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "wsi":
+        ap.error("--dump-outputs writes the default (wsi) mode's outputs; --mode %s has none to write" % args.mode)
 
     # `--gpus N` without a launcher: re-execute N ranks (one per device, rendezvous on 127.0.0.1) -- or exit non-zero when N devices are not
     # there.  Under torch.distributed.run WORLD_SIZE must agree with --gpus.  A line with n_gpus < --gpus is never printed.

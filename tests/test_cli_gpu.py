@@ -156,7 +156,7 @@ def test_bench_contract_single_and_two_ranks(tmp_path):
     """bench.py (default mode: the whole slide job, here on a 3072^2 slide) prints ONE JSON line with the contract's keys; under
     torch.distributed.run with two ranks (both on this box's single GPU, host-staged gloo collectives -- RCCL refuses two ranks on
     one device) the SAME slide is sharded into two bands (strong scaling) and labelled band-locally with a halo exchange."""
-    one = _bench([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--slide", "3072"])
+    one = _bench([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--slide", "3072"])
     for k in CONTRACT_KEYS:
         assert k in one, k
     ts = one["train_step"]  # BASELINE configs[4] rides along in the default line: batch 16 x 448^2, three timed steps
@@ -169,8 +169,9 @@ def test_bench_contract_single_and_two_ranks(tmp_path):
     assert 0.25 < rf["frac"] <= 1.0, rf  # the share of the fp32 MFMA roof the kernel's own instructions fill
     # F(4x4,3x3) executes 36 of the direct convolution's 144 multiplies per 4x4 outputs (F(2x2,3x3): 16 of 36)
     assert abs(rf["algorithmic_tflops"] - rf["achieved"] * (4.0 if rf["kernel"].startswith("conv_wino4") else 36 / 16)) < 0.5
-    assert abs(one["value"] - 3072 * 3072 / (one["ms_per_step"] * 1e-3 * 3) / 1e6) / one["value"] < 0.01
+    assert abs(one["value"] - 3072 * 3072 / (one["ms_per_step"] * 1e-3) / 1e6) / one["value"] < 0.01
     assert one["config"]["inference_Mpx_s"] > one["value"] and one["config"]["whole_job_s"] >= one["config"]["inference_s"]
+    assert abs(one["config"]["whole_job_s"] - one["ms_per_step"] * 1e-3) < 2e-3, one["config"]  # a step is one whole job: K steps, K jobs
     kern = {r["kernel"]: r for r in one["kernels"]}
     assert "head_group" in kern and abs(sum(r["share"] for r in one["kernels"]) - 1.0) < 0.01
     for t in ("Nuclei", "Gland", "Lumen"):
@@ -187,7 +188,7 @@ def test_bench_contract_single_and_two_ranks(tmp_path):
     two = _bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
                   "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--slide", "3072"])
     assert two["n_gpus"] == 2 and "cpu_baseline" not in two and two["scaling"] == "strong"
-    assert abs(two["value"] - 3072 * 3072 / (two["ms_per_step"] * 1e-3 * 3) / 1e6) / two["value"] < 0.01
+    assert abs(two["value"] - 3072 * 3072 / (two["ms_per_step"] * 1e-3) / 1e6) / two["value"] < 0.01
     # same slide, same instances: band-local labelling with the halo exchange finds exactly what one GPU finds
     for t in ("Nuclei", "Gland", "Lumen"):
         assert two["postproc"][t]["n_inst"] == one["postproc"][t]["n_inst"], (t, one["postproc"][t], two["postproc"][t])
@@ -210,11 +211,11 @@ def test_bench_contract_eight_ranks_time_sharing_one_gpu():
         assert len(lines) == 1, r.stdout[-2000:]
         return json.loads(lines[0])
 
-    one = run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "8192"])
+    one = run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "8192"])
     eight = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", "29541",
-                 "bench.py", "--gpus", "8", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--slide", "8192", "--streams", "1"])  # (eight ranks share ONE GPU's HBM here: no second handle each)
+                 "bench.py", "--gpus", "8", "--full", "--steps", "4", "--warmup", "1", "--backend", "gloo", "--slide", "8192", "--streams", "1"])  # (eight ranks share ONE GPU's HBM here: no second handle each)
     assert eight["n_gpus"] == 8 and eight["scaling"] == "strong" and eight["config"]["tiles"] == 1024 and "cpu_baseline" not in eight and "train_step" not in eight
-    assert abs(eight["value"] - 8192 * 8192 / (eight["ms_per_step"] * 1e-3 * 4) / 1e6) / eight["value"] < 0.01
+    assert abs(eight["value"] - 8192 * 8192 / (eight["ms_per_step"] * 1e-3) / 1e6) / eight["value"] < 0.01
     for t in ("Nuclei", "Gland", "Lumen"):
         assert eight["postproc"][t]["n_inst"] == one["postproc"][t]["n_inst"] > 10, (t, one["postproc"][t], eight["postproc"][t])
         assert eight["postproc"][t]["n_truncated"] == 0 and eight["postproc"][t]["n_unresolved"] == 0, eight["postproc"][t]
@@ -227,15 +228,33 @@ def test_bench_contract_eight_ranks_time_sharing_one_gpu():
     assert pr["bytes_into_rank0"]["ratio"] >= 20.0 and pr["tables_and_contours_s_slowest_rank"] > 0, pr
 
 
-def test_bench_nccl_branch_at_world_one():
+def test_bench_nccl_branch_at_world_one(tmp_path):
     """The RCCL code path on the hardware there is: `init_process_group("nccl", device_id=...)`, the warm-up gather, run_distributed's
     all-gathers and the label / class-map gathers on CUDA tensors all execute with ONE rank (RCCL accepts a single-rank communicator),
-    and the result equals the plain single-process run."""
-    ref = _bench([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "2048"])
-    one = _bench([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "2048", "--force-dist", "--backend", "nccl"])
+    and the result equals the plain single-process run: the same instance counts, and the same outputs in the samples --dump-outputs
+    writes (class maps and probability canvases equal, label maps equal up to a renaming of the ids)."""
+    da, db = tmp_path / "ref", tmp_path / "one"
+    ref = _bench([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "2048",
+                  "--dump-outputs", str(da)])
+    one = _bench([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-train-leg", "--no-ingest-leg", "--slide", "2048", "--force-dist", "--backend", "nccl",
+                  "--dump-outputs", str(db)])
     assert one["n_gpus"] == 1 and one["multi_gpu"] is not None and "root_gather" in one["multi_gpu"]
     for t in ("Nuclei", "Gland", "Lumen"):
         assert one["postproc"][t]["n_inst"] == ref["postproc"][t]["n_inst"]
+    names = sorted(os.listdir(str(da)))
+    assert names == sorted(os.listdir(str(db))) and sum(os.path.getsize(str(da / n)) for n in names) <= 64 << 20, names
+    for t in ("Nuclei", "Gland", "Lumen"):
+        assert "labels_%s.npy" % t in names and "canvas_%s-INST.npy" % t in names, names
+    assert any(n.startswith("classes_") for n in names), names
+    for n in names:
+        a, b = np.load(str(da / n)), np.load(str(db / n))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape and a.size > 0, n
+        if n.startswith("labels_"):  # one id on one side <-> one id on the other, background on both sides alike
+            pairs = np.unique(np.stack([a, b], 1), axis=0)
+            assert len(np.unique(pairs[:, 0])) == len(pairs) == len(np.unique(pairs[:, 1])) and np.array_equal(a == 0, b == 0), n
+            assert (a > 0).any(), n
+        else:
+            assert np.array_equal(a, b), n
 
 
 def test_bench_batch_mode_two_ranks():
@@ -746,7 +765,7 @@ def test_bench_configs2_slide_20000_full_size_one_vs_three_local_bands():
     a window (n_truncated == 0), the SAME instance counts either way, and the tail consuming the class canvases this job's inference wrote
     (bench.py checks their checksums against the canvases).  The one-band line is what profiles/r05_bench_wsi_20000.json holds."""
     common = [sys.executable, "bench.py", "--slide", "20000", "--steps", "4", "--warmup", "1", "--no-train-leg", "--no-ingest-leg", "--no-cpu-baseline", "--no-dat", "--no-ref-tiling"]
-    one = _bench(common + ["--max-band-mpx", "420"], timeout=1500)
+    one = _bench(common + ["--max-band-mpx", "420", "--full"], timeout=1500)
     three = _bench(common + ["--max-band-mpx", "150"], timeout=1500)
     assert one["config"]["slide"] == [20000, 20000] and one["config"]["tiles"] == 6241 and "configs[2]" in one["config"]["workload"]
     assert one["postproc"]["Nuclei"]["local_bands"] == 1 and three["postproc"]["Nuclei"]["local_bands"] >= 3

@@ -37,6 +37,33 @@ def test_bench_gpus_n_without_launcher_refuses_instead_of_running_one_gpu():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_sample_is_seeded_and_typed(tmp_path):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): a strided view larger than the sample is sampled at the same seeded row-major positions
+    every time, floats as float32, integers as float64 with every id kept exactly; small arrays are written whole; other modes refuse the option."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    full = torch.arange(1200 * 1000 * 2, dtype=torch.float32).reshape(1200, 1000, 2)
+    view = full[:1100, :900]
+    lab = torch.randint(0, 2 ** 31 - 1, (900, 1300), dtype=torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"canvas_x": view, "labels_y": lab, "classes_z@0.25": np.arange(12, dtype=np.uint8).reshape(3, 4)})
+    a = {n: np.load(str(tmp_path / "a" / n)) for n in os.listdir(str(tmp_path / "a"))}
+    assert sorted(a) == ["canvas_x.npy", "classes_z_at_0.25.npy", "labels_y.npy"]
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / n))), n
+    idx = np.unique(np.random.RandomState(0).randint(0, view.numel(), bench.DUMP_SAMPLE, dtype=np.int64))
+    assert a["canvas_x.npy"].dtype == np.float32 and np.array_equal(a["canvas_x.npy"], view.contiguous().reshape(-1).numpy()[idx])
+    idx = np.unique(np.random.RandomState(0).randint(0, lab.numel(), bench.DUMP_SAMPLE, dtype=np.int64))
+    assert a["labels_y.npy"].dtype == np.float64 and np.array_equal(a["labels_y.npy"].astype(np.int64), lab.reshape(-1).numpy()[idx].astype(np.int64))
+    assert np.array_equal(a["classes_z_at_0.25.npy"], np.arange(12, dtype=np.float64))
+    r = subprocess.run([sys.executable, "bench.py", "--mode", "batch", "--dump-outputs", str(tmp_path / "c")], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT, env=_clean_env())
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and not os.path.exists(str(tmp_path / "c"))
+
+
 def test_bench_gpus_disagreeing_with_world_size_refuses():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--mode", "batch"], capture_output=True, text=True, timeout=300, cwd=ROOT,
                        env=_clean_env(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())))
