@@ -5,6 +5,7 @@ Host mirrors of the reference interface (same names / argument meaning):
   cerberus_amd.run_desc.infer_step                  <- reference models/run_desc.py:439-502
   cerberus_amd.postproc.PostProcInstErodedContourMap <- reference loader/postproc.py:268-407
   cerberus_amd.tile / cerberus_amd.wsi              <- reference infer/tile.py, infer/wsi.py (geometry + stitching)
+  cerberus_amd.targets.gen_targets (+ _batch)       <- reference loader/targets.py:185-244 with loader/augs.py fix_mirror_padding
 All arithmetic runs in libcerberus_hip.so (include/cerberus_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

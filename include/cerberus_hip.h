@@ -358,6 +358,43 @@ int cerb_head_loss_wmap(const float* logits, long long stride_n, long long strid
                         const float* pixel_weight, float ce_weight, float dice_weight, float head_weight, int patch_class_mode,
                         float* loss_out, float* dlogits, void* ws, size_t ws_bytes, void* hip_stream);
 
+/* ---- training targets on the device: gen_targets (loader/targets.py:185-244) with fix_mirror_padding (loader/augs.py:7-21) --------------
+ * ann: device int32 [n][h][w][c] instance / class annotations (what the reference's dataset hands gen_targets, batched).  A call handles up to
+ * CERB_TARGET_MAX_HEADS heads of ONE kind over all n samples in batched launches; head i reads channel chan[i].  Outputs are [heads][n][crop_h]
+ * [crop_w], centre-cropped with the reference's offset int((h - crop_h) * 0.5) (misc/utils.py:94-99).
+ * cerb_target_pixel_maps : IP / NP (flag[i] = 1: binarise, loader/targets.py:61-65,169-175) and TP / PC (flag[i] = 0: pass through, :160-166,178-182).
+ * cerb_target_eroded_maps: IP-ERODED-k (flag[i] = 0: inner map 0 / 1) and IP-ERODED-CONTOUR-k (flag[i] = 1: inner + 2 * contour), ksize[i] = k
+ *                          (odd, 3..11; OpenCV's MORPH_ELLIPSE row spans, cerb_target_element).  Instances are the 4-connected components of equal
+ *                          non-zero id (fix_mirror_padding's partition); only those with a pixel inside the crop count (:77-79,121-123); out-of-image
+ *                          taps are ignored by erode and dilate.  meta != NULL: also labels the inner maps (scipy.ndimage.label's partition, :90,139)
+ *                          for cerb_target_weight_maps and leaves in meta (device int32 [2 + heads * n]) the summed area of the labels' windows
+ *                          (meta[0..1], one 64-bit count) and per image e = head * n_samples + sample its number of labels (meta[2 + e]).
+ *                          ws: cerb_target_workspace_bytes(heads * n, h, w) bytes (25 B per pixel), kept untouched until cerb_target_weight_maps ran.
+ * cerb_target_weight_maps: unet_weight_map (:12-58) + 1 for the maps cerb_target_eroded_maps labelled into ws: per label the exact Euclidean
+ *                          distance inside its bounding box grown by 10 pixels (1000 outside), the two smallest over labels, w = 1 + 10 exp(-((d1 + d2)
+ *                          / k)^2 / 2), 1 on labels and in maps with fewer than two labels.  max_labels >= every meta[2 + e], total_area = the 64-bit
+ *                          meta[0..1]; win_ws: cerb_target_window_workspace_bytes(heads * n, max_labels, total_area) bytes.  dsum_out (optional):
+ *                          d1 + d2 in float32 before the exponential (2000 in maps with fewer than two labels).  Squared distances are integers and
+ *                          the reduction is a gather per pixel: results are bitwise reproducible.
+ * cerb_target_element    : the k x k MORPH_ELLIPSE element (host bytes, 0 / 1) the morphology uses. */
+#define CERB_TARGET_MAX_HEADS 8
+typedef struct cerb_target_heads {
+    int n_heads;
+    int chan[CERB_TARGET_MAX_HEADS];
+    int ksize[CERB_TARGET_MAX_HEADS];
+    int flag[CERB_TARGET_MAX_HEADS];
+} cerb_target_heads;
+size_t cerb_target_workspace_bytes(int n_images, int h, int w);
+size_t cerb_target_window_workspace_bytes(int n_images, int max_labels, unsigned long long total_area);
+int cerb_target_element(int ksize, uint8_t* out);
+int cerb_target_pixel_maps(const int32_t* ann, int n, int h, int w, int c, const cerb_target_heads* heads, int crop_h, int crop_w,
+                           int32_t* out, void* hip_stream);
+int cerb_target_eroded_maps(const int32_t* ann, int n, int h, int w, int c, const cerb_target_heads* heads, int crop_h, int crop_w,
+                            int32_t* cls_out, int32_t* meta, void* ws, size_t ws_bytes, void* hip_stream);
+int cerb_target_weight_maps(int n, int h, int w, const cerb_target_heads* heads, int crop_h, int crop_w, const void* ws, size_t ws_bytes,
+                            int max_labels, unsigned long long total_area, void* win_ws, size_t win_ws_bytes, float* wmap_out,
+                            float* dsum_out, void* hip_stream);
+
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
 int cerb_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* synchronises on ev_stop */
