@@ -6,6 +6,15 @@ Host mirrors of the reference interface (same names / argument meaning):
   cerberus_amd.postproc.PostProcInstErodedContourMap <- reference loader/postproc.py:268-407
   cerberus_amd.tile / cerberus_amd.wsi              <- reference infer/tile.py, infer/wsi.py (geometry + stitching)
   cerberus_amd.targets.gen_targets (+ _batch)       <- reference loader/targets.py:185-244 with loader/augs.py fix_mirror_padding
+  cerberus_amd.valid_stats.ValidStats / valid_step_stats / validate <- reference models/run_desc.py:606-747 (ProcStepRawOutput) and :505-565
 All arithmetic runs in libcerberus_hip.so (include/cerberus_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):  # cerberus_amd.ValidStats / valid_step_stats / validate, imported on first use (the package import stays torch-free)
+    if name in ("ValidStats", "valid_step_stats", "validate"):
+        from . import valid_stats
+
+        return getattr(valid_stats, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -13,6 +13,7 @@ EXPORTS = [
     "cerb_net_profile_count", "cerb_net_profile_get", "cerb_net_set_conv_algo", "cerb_net_set_head_algo", "cerb_net_set_planar", "cerb_net_set_packed_items", "cerb_net_set_crop_roi", "cerb_net_set_fold_bn", "cerb_net_set_bn_eval", "cerb_net_begin_reload", "cerb_net_update_params", "cerb_net_forward_train", "cerb_net_train_grads", "cerb_net_grad_lookup", "cerb_copy_d2d", "cerb_adam_step", "cerb_adam_step_multi", "cerb_synth_slide", "cerb_gather_patches", "cerb_downsample2_inst", "cerb_half_size", "cerb_downsample2_inst_region", "cerb_pclass_tissue_map", "cerb_resample_box", "cerb_resample_area", "cerb_label_mask", "cerb_inst_table", "cerb_relabel", "cerb_head_loss_workspace_bytes", "cerb_head_loss", "cerb_head_loss_wmap", "cerb_inst_contour_start", "cerb_inst_contour_start_workspace_bytes", "cerb_inst_contour_count", "cerb_inst_contour_points",
     "cerb_target_workspace_bytes", "cerb_target_window_workspace_bytes", "cerb_target_element", "cerb_target_pixel_maps", "cerb_target_eroded_maps",
     "cerb_target_weight_maps",
+    "cerb_valid_stats_bytes", "cerb_valid_stats_reset", "cerb_valid_stats_accumulate",
 ]
 
 
@@ -62,6 +63,11 @@ class TrainStepIO(C.Structure):
 
 class TargetHeads(C.Structure):
     _fields_ = [("n_heads", C.c_int), ("chan", C.c_int * 8), ("ksize", C.c_int * 8), ("flag", C.c_int * 8)]
+
+
+class ValidHeads(C.Structure):
+    _fields_ = [("n_heads", C.c_int), ("kind", C.c_int * 8), ("n_classes", C.c_int * 8), ("pred_fmt", C.c_int * 8), ("true_fmt", C.c_int * 8),
+                ("pred", C.c_void_p * 8), ("true_map", C.c_void_p * 8)]
 
 
 class CerberusHipError(RuntimeError):
@@ -165,6 +171,10 @@ def lib():
                                           C.c_void_p, C.c_size_t, C.c_void_p]
     L.cerb_target_weight_maps.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(TargetHeads), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_ulonglong,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cerb_valid_stats_bytes.argtypes = [C.c_int]
+    L.cerb_valid_stats_bytes.restype = C.c_size_t
+    L.cerb_valid_stats_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.cerb_valid_stats_accumulate.argtypes = [C.POINTER(ValidHeads), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

@@ -395,6 +395,43 @@ int cerb_target_weight_maps(int n, int h, int w, const cerb_target_heads* heads,
                             int max_labels, unsigned long long total_area, void* win_ws, size_t win_ws_bytes, float* wmap_out,
                             float* dsum_out, void* hip_stream);
 
+/* ---- validation statistics on the device: ProcStepRawOutput (models/run_desc.py:606-747) over valid_step's read-outs (:332-436) ------------
+ * One grouped launch per step accumulates, per head and class, over_inter / over_total / over_correct / nr_pixels into a persistent device
+ * accumulator acc: int64 [n_heads][CERB_VALID_MAX_CLASSES][4] in that order (cerb_valid_stats_bytes(n_heads) bytes; rows of classes a head does
+ * not count stay 0).  flags: device bytes [n_heads][n], flags[head][sample] != 0 when the head's name appears anywhere in the sample's
+ * dummy_target row (:642); only flagged samples count.  Per flagged sample, with p the prediction and t the true map, both [n][h][w]:
+ *   CERB_VALID_INST  (:646-660) classes k = 1 .. C-1: pred_ = (p[..., k-1] > 0.5) * k; inter = #(pred_ == k and t == k), total = #(pred_ == k) +
+ *                    #(t == k), correct = #(t == pred_) -- background agreeing with 0 included.  p: float32 [n][h][w][C-1] (softmax channels 1:).
+ *   CERB_VALID_TYPE  (:661-674) classes k = 1 .. C-1: inter and total as above on p == k, counted only where t > 0; correct = #(t == p) without the
+ *                    mask, the same number for every class.  p: class ids, uint8 (pred_fmt 0) or int64 (pred_fmt 1) [n][h][w].
+ *   CERB_VALID_PATCH (:675-686) classes k = 0 .. C-1: as TYPE without the mask.  p: float32 class ids, the tile-broadcast map [n][h][w] (pred_fmt 0)
+ *                    or one value per sample [n] (pred_fmt 1).
+ *   every head       nr_pixels += h * w (:633,641).
+ * t: int32 (true_fmt bit 0 clear) or float32 (bit 0 set) [n][h][w]; Patch-Class may give one value per sample [n] (bit 1 set).  Class ids are
+ * compared as float32 (numpy's comparison of the reference's float32 maps); int32 ids must stay below 2^24 in magnitude.  NaN compares false.
+ * The reference defines these statistics only for batches without a Patch-Class target (with one, its valid_step hands back [n][h][h][w] true
+ * arrays that cannot be compared, and the callback raises); here the same per-head rules run on the natural [n][h][w] maps in both cases.
+ * Counts are integers: the accumulator is independent of the order of blocks and bitwise reproducible.  No host synchronisation, no allocation;
+ * the launch and cerb_valid_stats_reset (an asynchronous clear) run on hip_stream.  The summary (:526-561) is host arithmetic:
+ * accuracy = (correct + 1e-8) / (nr_pixels + 1e-8), dice = 2 inter / (total + 1e-8), in float64 (cerberus_amd/valid_stats.py). */
+#define CERB_VALID_MAX_HEADS 8
+#define CERB_VALID_MAX_CLASSES 16
+#define CERB_VALID_INST 0
+#define CERB_VALID_TYPE 1
+#define CERB_VALID_PATCH 2
+typedef struct cerb_valid_heads {
+    int n_heads;
+    int kind[CERB_VALID_MAX_HEADS];
+    int n_classes[CERB_VALID_MAX_HEADS];
+    int pred_fmt[CERB_VALID_MAX_HEADS];
+    int true_fmt[CERB_VALID_MAX_HEADS];
+    const void* pred[CERB_VALID_MAX_HEADS];
+    const void* true_map[CERB_VALID_MAX_HEADS];
+} cerb_valid_heads;
+size_t cerb_valid_stats_bytes(int n_heads);
+int cerb_valid_stats_reset(int64_t* acc, int n_heads, void* hip_stream);
+int cerb_valid_stats_accumulate(const cerb_valid_heads* heads, const uint8_t* flags, int n, int h, int w, int64_t* acc, void* hip_stream);
+
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
 int cerb_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* synchronises on ev_stop */
