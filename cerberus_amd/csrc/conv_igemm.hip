@@ -26,25 +26,7 @@
 // arithmetic: every global access is  uniform base (SGPRs, advanced by the scalar unit)  +  a per-lane 32-bit byte offset
 // computed ONCE per kernel  (+ immediate), every LDS access is  per-lane base + immediate,  and image-border handling
 // (zero padding) is a uniform branch taken only by items that touch the border.
-#include "cerb_common.h"
-
-// Buffer-resource addressing: address = descriptor base (4 SGPRs, built by the scalar unit per item) + per-lane 32-bit byte
-// offset (VGPR, kernel-invariant) + uniform byte offset (SGPR) -- no VALU instruction per access.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);  // raw buffer, no range clipping
-}
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
-}
-__device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff, 0);
-    // gfx950 hazard hipcc (ROCm 7.2) does not pad: buffer_store_dwordx4 whose soffset is an SGPR, followed directly by a VALU
-    // write of its data VGPRs, stores corrupted data (the compiler only inserts wait states for the immediate-soffset form).
-    // Found as run-to-run differing outputs; two wait states pinned behind the store cure it (scripts/dev_wrace.sh).
-    asm volatile("s_nop 1");
-    __builtin_amdgcn_sched_barrier(0);
-}
+#include "wino_common.h"  // buffer-resource addressing: make_rsrc, buf_load, buf_store (with the gfx950 store-hazard padding)
 
 __device__ __forceinline__ f32x4 splat4(float x) {
     f32x4 r = {x, x, x, x};

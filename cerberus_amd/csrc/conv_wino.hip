@@ -26,7 +26,7 @@
 // tensor and from an explicit mask (uniform branch, border items only) for everything else.
 #include <type_traits>
 
-#include "cerb_common.h"
+#include "wino_common.h"
 
 namespace {
 constexpr int WTY = 4, WTX = 8;          // Winograd tiles per workgroup
@@ -45,24 +45,10 @@ constexpr int NPRE = 4;                  // extra weight steps of the NEXT item 
 constexpr int CHUNK_W_BYTES = 16 * 4 * 2 * 1024;  // packed weights of one (cout block, chunk): 128 KiB
 constexpr int WAVE_W_BYTES = 4 * 4 * 2 * 1024;    // one wave's share of it
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
-}
-__device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
+// cache policy of the output stores; buf_store (wino_common.h) carries the gfx950 store-hazard padding (tests/test_isa_hazard.py)
 #ifndef WINO_STORE_AUX
 #define WINO_STORE_AUX 0
 #endif
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff, WINO_STORE_AUX);
-    // gfx950 hazard hipcc (ROCm 7.2) does not pad: buffer_store_dwordx4 whose soffset is an SGPR, followed directly by a VALU
-    // write of its data VGPRs, stores corrupted data (the compiler only inserts wait states for the immediate-soffset form).
-    // Found as run-to-run differing outputs; two wait states pinned behind the store cure it (scripts/dev_wrace.sh).
-    asm volatile("s_nop 1");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 struct Item {
     int g, cb, n, oy0, ox0, tx, ty;
@@ -479,7 +465,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_kernel(ConvParams p) {
                     o[1] = fmaxf(o[1], floor_);
                     o[2] = fmaxf(o[2], floor_);
                     o[3] = fmaxf(o[3], floor_);
-                    buf_store(o, r_out, vo, (2 * k + i) * orow);
+                    buf_store<WINO_STORE_AUX>(o, r_out, vo, (2 * k + i) * orow);
                 }
             }
         }

@@ -21,16 +21,14 @@
 // Reference layers: models/utils/conv_layers.py:24-60 (_ConvLayer) and models/backbone/resnet.py:81-97 (BasicBlock).
 #include <type_traits>
 
-#include "cerb_common.h"
+#include "wino_common.h"
 
 namespace {
 constexpr int NPOS = 36;
 constexpr int NT = 32;                        // tiles per item: two blocks of 4x4 tiles
-constexpr int BLK = 16;                       // a block is 16x16 output pixels
 constexpr int CB = 16;                        // input channels per LDS pass
 constexpr int V_FLOATS = NPOS * NT * CB;      // one V buffer: 72 KiB
 constexpr int LDS_BYTES = 2 * V_FLOATS * 4;   // double-buffered: 144 KiB
-constexpr int OPX = 68;                       // output staging: floats per pixel (64 channels + 4: bank skew)
 static_assert(256 * OPX + 16 <= V_FLOATS, "a block's outputs are staged in one V buffer");
 #ifdef W4_PROF
 constexpr int PROF_BYTES = 16 * 40 * 8;
@@ -81,28 +79,6 @@ static_assert(P0 + (36 + PL - 1) / PL <= TQ && TQ + 13 < NS, "the patch must be 
 constexpr int BIAS_XI = 7;                    // A^T[i][1] A[1][j] = 1 for all 16 outputs: the bias enters through position (1, 1)
 constexpr int CHUNK_W_BYTES = NPOS * 4 * 1024;  // packed weights of one (cout block, 16-channel chunk): 144 KiB
 constexpr int WAVE_W_BYTES = NPOS * 1024;       // one wave's share: 36 steps x 1 KiB
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
-}
-// the input patch: 2 GiB of range, so that a lane offset of 0x80000000 is out of range and the hardware returns zeros (conv_wino4b.hip)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_lim(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0));
-}
-__device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff, W4_STORE_AUX);
-    asm volatile("s_nop 1");  // gfx950 store hazard, see conv_wino.hip buf_store / tests/test_isa_hazard.py
-    __builtin_amdgcn_sched_barrier(0);
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 buf_load2(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, W4_PATCH_AUX));
-}
 
 #ifdef W4_PROF
 // developer instrumentation (scripts/dev_w4prof.py): wave 0 of workgroup W4_PROF stamps s_memtime at every step of its second item
@@ -228,7 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     };
     auto issue = [&](__amdgpu_buffer_rsrc_t r, const EdgeOff& e, int chunk_off, int k) __attribute__((always_inline)) {
         const int rr = k / 6, qq = k % 6;
-        d[rr][qq] = buf_load2(r, e.o[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + rr * rowb + qq * pixb);
+        d[rr][qq] = buf_load2<W4_PATCH_AUX>(r, e.o[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + rr * rowb + qq * pixb);
     };
     auto mask_border = [&](const Blk& b) __attribute__((always_inline)) {
         const f32x2 z = {0.f, 0.f};
@@ -241,41 +217,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 d[r][q] = ok ? d[r][q] : z;
             }
     };
-    // B^T x for the points (0, 1, -1, 2, -2, inf), in place: 12 packed operations.  Written as v_pk_fma_f32 / v_pk_add_f32 by hand: hipcc
-    // (ROCm 7.2) scalarises vector subtractions and multiplies by negative literals (116 v_fma_f32 + 44 v_add_f32 + 64 packed instructions
-    // per chunk instead of 144 packed ones), and every VALU instruction of this wave is a matrix-pipe cycle lost (one wave per SIMD).
+    // B^T x, in place (wino_common.h: wino4_bt6), with its constants pinned in registers
     f32x2 k2 = {2.f, 2.f}, k4 = {4.f, 4.f}, k5 = {5.f, 5.f};
     asm volatile("" : "+v"(k2), "+v"(k4), "+v"(k5));
-    auto bt6 = [&](f32x2& x0, f32x2& x1, f32x2& x2, f32x2& x3, f32x2& x4, f32x2& x5) __attribute__((always_inline)) {
-#ifdef W4_C_XF
-        const f32x2 t0 = x4 - 4.f * x2, t1 = x3 - 4.f * x1;
-        const f32x2 u0 = x4 - x2, u1 = x3 - x1;
-        x0 = (4.f * x0 + x4) - 5.f * x2;
-        x5 = (4.f * x1 + x5) - 5.f * x3;
-        x1 = t0 + t1;
-        x2 = t0 - t1;
-        x3 = u0 + 2.f * u1;
-        x4 = u0 - 2.f * u1;
-#else
-        f32x2 t0, t1, u0, u1;
-        asm("v_pk_fma_f32 %6, %2, %11, %4 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t0 = x4 - 4 x2
-            "v_pk_fma_f32 %7, %1, %11, %3 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t1 = x3 - 4 x1
-            "v_pk_add_f32 %8, %4, %2 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u0 = x4 - x2
-            "v_pk_add_f32 %9, %3, %1 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u1 = x3 - x1
-            "v_pk_fma_f32 %0, %0, %11, %4\n\t"                                  // x0 = 4 x0 + x4
-            "v_pk_fma_f32 %5, %1, %11, %5\n\t"                                  // x5 = 4 x1 + x5
-            "v_pk_fma_f32 %0, %2, %12, %0 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x0 -= 5 x2
-            "v_pk_fma_f32 %5, %3, %12, %5 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x5 -= 5 x3
-            "v_pk_add_f32 %1, %6, %7\n\t"                                       // x1 = t0 + t1
-            "v_pk_add_f32 %2, %6, %7 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // x2 = t0 - t1
-            "v_pk_fma_f32 %3, %9, %10, %8\n\t"                                  // x3 = u0 + 2 u1
-            "v_pk_fma_f32 %4, %9, %10, %8 neg_lo:[1,0,0] neg_hi:[1,0,0]"         // x4 = u0 - 2 u1
-            : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "=&v"(t0), "=&v"(t1), "=&v"(u0), "=&v"(u1)
-            : "v"(k2), "v"(k4), "v"(k5));
-#endif
-    };
-    auto pass_v = [&](int q) { bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q]); };  // down column q
-    auto pass_h = [&](int r) { bt6(d[r][0], d[r][1], d[r][2], d[r][3], d[r][4], d[r][5]); };  // along row r
+    auto pass_v = [&](int q) { wino4_bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q], k2, k4, k5); };  // down column q
+    auto pass_h = [&](int r) { wino4_bt6(d[r][0], d[r][1], d[r][2], d[r][3], d[r][4], d[r][5], k2, k4, k5); };  // along row r
     auto write_row = [&](int buf, int r) {
 #pragma unroll
         for (int b = 0; b < 6; ++b) *reinterpret_cast<f32x2*>(lds + buf * V_FLOATS + (r * 6 + b) * NT * CB + vw) = d[r][b];
@@ -430,148 +376,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int dd = WD; dd < PRE; ++dd) wq[dd % RING] = buf_load(rw_nx, wlane, dd * 1024);
         load_bias(wnx);
         {
-            // The wave's results are 64-byte pieces (16 channels) of pixels 4 apart: stored directly, one instruction touches 16 partial
-            // cache lines and takes ~300 cycles to issue, with the matrix pipe idle (measured: 8 k of an item's 80 k cycles).  The four
-            // waves therefore transpose each block through the V buffer the last chunk has finished with (64 KiB + skew of its 72):
-            // [pixel][64 channels], and store whole pixel rows -- 1 KiB contiguous (4 pixels x 256 bytes) per instruction.
             int lane_o = lane;
-            asm volatile("" : "+v"(lane_o));  // recomputed per item: keeps these out of the MFMA phase's register budget
-            const int mo = lane_o & 15, kso = lane_o >> 4;
-            float* stg = lds + (vbuf ^ 1) * V_FLOATS;
-            // write side: lane (tile mo, channel quad kso) owns pixels (4 ty + i, 4 tx + j); pixel stride 68 floats, 4 floats of skew per tile row
-            const int sw = ((64 * (mo >> 2) + 4 * (mo & 3)) * OPX + 4 * (mo >> 2) + 16 * a + 4 * kso);
-            // read side: wave a stores pixel rows 4 a .. 4 a + 3; lane = (pixel lane_o >> 4 of a group of four, 16-byte piece lane_o & 15)
-            const int sr = ((64 * a + (lane_o >> 4)) * OPX + 4 * a + 4 * (lane_o & 15));
-            const int orow = p.Wo * p.Cout * 4, opix = p.Cout * 4;
-            const unsigned ooff = (unsigned)(((4 * a * p.Wo + (lane_o >> 4)) * p.Cout + 4 * (lane_o & 15)) * 4);
-            const float floor_ = p.relu ? 0.f : -3.402823466e38f;
-            const unsigned span = (unsigned)(BLK * p.Wo * p.Cout * 4);
+            asm volatile("" : "+v"(lane_o));  // recomputed per item: keeps what derives from it out of the MFMA phase's register budget
+            float* stg = lds + (vbuf ^ 1) * V_FLOATS;  // the V buffer the last chunk has finished with; the next item's second chunk rewrites it
 #pragma unroll
             for (int tb = 0; tb < 2; ++tb) {
                 const Blk bo = tb ? w.b1 : w.b0;
-                const int by0 = oy0(bo), bx0 = ox0(bo);
-                const long long origin = (((long long)bo.n * p.Ho + by0) * p.Wo + bx0) * p.Cout + w.cb * 64;  // floats, uniform
-                const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(p.out + w.g * p.out_gs + origin, 0, span, 0x00020000);
-                const bool partial = (by0 + BLK > p.Ho) || (bx0 + BLK > p.Wo);
-                const bool dead = (tb == 1 && w.nvalid == 1);
                 W4_STAMP(1 + 3 * tb);
-                // vertical pass: T[i][b] = sum_a A^T[i][a] M[a][b]
-                f32x4 T[4][6];
-#pragma unroll
-                for (int b = 0; b < 6; ++b) {
-                    const f32x4 m0 = acc[0 * 6 + b][tb], m1 = acc[1 * 6 + b][tb], m2 = acc[2 * 6 + b][tb], m3 = acc[3 * 6 + b][tb],
-                                m4 = acc[4 * 6 + b][tb], m5 = acc[5 * 6 + b][tb];
-                    const f32x4 s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-                    T[0][b] = m0 + s1 + s2;
-                    T[1][b] = d1 + 2.f * d2;
-                    T[2][b] = s1 + 4.f * s2;
-                    T[3][b] = (d1 + 8.f * d2) + m5;
-                }
-                W4_STAMP(2 + 3 * tb);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x4 s1 = T[i][1] + T[i][2], d1 = T[i][1] - T[i][2], s2 = T[i][3] + T[i][4], d2 = T[i][3] - T[i][4];
-                    *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 0) * OPX) = T[i][0] + s1 + s2;
-                    *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 1) * OPX) = d1 + 2.f * d2;
-                    *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 2) * OPX) = s1 + 4.f * s2;
-                    *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 3) * OPX) = (d1 + 8.f * d2) + T[i][5];
-                }
-                __syncthreads();
-                // 16 groups of four pixels per wave: row 4 a + (k >> 2), pixels 4 (k & 3) .. + 3
-                unsigned vo[4];
-#pragma unroll
-                for (int x4 = 0; x4 < 4; ++x4) {
-                    const bool ok = !dead && (!partial || (bx0 + 4 * x4 + (lane_o >> 4) < p.Wo));
-                    vo[x4] = ok ? ooff : 0x80000000u;  // out-of-range offsets: the hardware drops the store / returns 0
-                }
-                f32x4 res[16];
-                if (HAS_RES) {
-                    const __amdgpu_buffer_rsrc_t r_res =
-                        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.resid + w.g * p.resid_gs + origin), 0, span, 0x00020000);
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                        res[k] = buf_load(r_res, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + 4 * (k & 3) * opix);
-                    }
-                }
-                // (requested here, behind the staging barrier; requested before the output transform instead: no faster, and one instantiation of conv_wino4b spilled)
-                f32x4 yv[STATS == 2 ? 16 : 1], bm, brs, bga, bbe;  // STATS 2: the BatchNorm's input at this lane's pixels, its parameters for this lane's four channels
-                if constexpr (STATS == 2) {
-                    const __amdgpu_buffer_rsrc_t r_y =
-                        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bst_y + w.g * p.bst_y_gs + origin), 0, span, 0x00020000);
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                        yv[k] = buf_load(r_y, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + 4 * (k & 3) * opix);
-                    }
-                    const int pc = w.g * p.Cout + w.cb * 64 + 4 * (lane_o & 15);
-                    bm = *reinterpret_cast<const f32x4*>(p.bst_mean + pc);
-                    brs = *reinterpret_cast<const f32x4*>(p.bst_rstd + pc);
-                    bga = *reinterpret_cast<const f32x4*>(p.bst_gamma + pc);
-                    bbe = *reinterpret_cast<const f32x4*>(p.bst_beta + pc);
-                }
-                f32x4 bts = {0.f, 0.f, 0.f, 0.f}, btq = {0.f, 0.f, 0.f, 0.f};  // STATS: this lane's 16 pixels x 4 channels
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    f32x4 o = *reinterpret_cast<const f32x4*>(stg + sr + (16 * (k >> 2) + 4 * (k & 3)) * OPX);
-                    if (HAS_RES) o = o + res[k];
-                    o[0] = fmaxf(o[0], floor_);
-                    o[1] = fmaxf(o[1], floor_);
-                    o[2] = fmaxf(o[2], floor_);
-                    o[3] = fmaxf(o[3], floor_);
-                    const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                    if constexpr (STATS == 1) {
-                        if (rowok && vo[k & 3] != 0x80000000u) {  // pixels inside the image only
-                            bts = bts + o;
-                            btq[0] = fmaf(o[0], o[0], btq[0]);
-                            btq[1] = fmaf(o[1], o[1], btq[1]);
-                            btq[2] = fmaf(o[2], o[2], btq[2]);
-                            btq[3] = fmaf(o[3], o[3], btq[3]);
-                        }
-                    }
-                    if constexpr (STATS == 2) {
-                        if (rowok && vo[k & 3] != 0x80000000u) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {  // the mask by the ONE expression every BatchNorm kernel uses (train_kernels.hip: bn_out): identical ReLU masks
-                                const float yy = yv[k][e];
-                                const float z = __fmaf_rn(yy - bm[e], brs[e] * bga[e], bbe[e]);
-                                const float g = z > 0.f ? o[e] : 0.f;
-                                bts[e] += g;
-                                btq[e] = fmaf(g, (yy - bm[e]) * brs[e], btq[e]);
-                            }
-                        }
-                    }
-#ifndef W4_ABL_NOSTORE
-                    buf_store(o, r_out, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + 4 * (k & 3) * opix);
-#else
-                    if (o[0] == 1.2345e-30f) buf_store(o, r_out, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + 4 * (k & 3) * opix);
-#endif
-                }
-                if constexpr (STATS) {  // the four lanes that hold a channel quad, then (behind the barrier) the four waves = the block's 256 pixels
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        bts[e] += __shfl_xor(bts[e], 16);
-                        bts[e] += __shfl_xor(bts[e], 32);
-                        btq[e] += __shfl_xor(btq[e], 16);
-                        btq[e] += __shfl_xor(btq[e], 32);
-                    }
-                    if (lane_o < 16) {
-                        *reinterpret_cast<f32x4*>(bnred + (a * 16 + lane_o) * 8) = bts;
-                        *reinterpret_cast<f32x4*>(bnred + (a * 16 + lane_o) * 8 + 4) = btq;
-                    }
-                }
-                __syncthreads();  // the staging buffer is rewritten by the next block, then by the next item's second chunk
-                if constexpr (STATS) {
-                    if (a == 0 && lane_o < 16 && !dead && p.bn_part) {
-                        const long long blk = ((long long)bo.n * p.tiles_y + bo.by) * p.tiles_x + bo.bx;
-                        double* dst = p.bn_part + (((long long)w.g * p.bn_bpg + blk) * p.Cout + w.cb * 64 + 4 * lane_o) * 2;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            dst[2 * e] = (double)(((bnred[lane_o * 8 + e] + bnred[(16 + lane_o) * 8 + e]) + bnred[(32 + lane_o) * 8 + e]) + bnred[(48 + lane_o) * 8 + e]);
-                            dst[2 * e + 1] = (double)(((bnred[lane_o * 8 + 4 + e] + bnred[(16 + lane_o) * 8 + 4 + e]) + bnred[(32 + lane_o) * 8 + 4 + e]) + bnred[(48 + lane_o) * 8 + 4 + e]);
-                        }
-                    }
-                }
+                wino4_store_block<HAS_RES, STATS, false, 0, W4_STORE_AUX>(
+                    p, stg, bnred, a, lane_o, Wino4Block{w.g, w.cb, bo.n, bo.by, bo.bx}, tb == 1 && w.nvalid == 1,
+                    [&](int xi) __attribute__((always_inline)) -> const f32x4& { return acc[xi][tb]; }, [](int, int&, int&, int&) {},
+                    [&](int k) __attribute__((always_inline)) { if (k == 0) W4_STAMP(2 + 3 * tb); });
             }
         }
 #ifdef W4_PROF
@@ -593,30 +408,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 template <bool HAS_RES>
 static hipError_t launch_wino4(ConvParams p, hipStream_t st) {
-    p.tiles_x = (p.Wo + BLK - 1) / BLK;  // blocks, not tiles
-    p.tiles_y = (p.Ho + BLK - 1) / BLK;
-    p.ty_off = p.tx_off = 0;
-    if (p.roi_y1 > p.roi_y0 && p.roi_x1 > p.roi_x0) {
-        p.ty_off = p.roi_y0 / BLK;
-        p.tx_off = p.roi_x0 / BLK;
-        p.tiles_y = (p.roi_y1 + BLK - 1) / BLK - p.ty_off;
-        p.tiles_x = (p.roi_x1 + BLK - 1) / BLK - p.tx_off;
-    }
-    const long long nblk = (long long)p.N * p.tiles_x * p.tiles_y;
+    const long long nblk = wino4_block_grid(p);
     const long long items = (long long)p.groups * ((nblk + 1) / 2) * (p.Cout / 64);
-    const int stats = p.bn_part == nullptr ? 0 : (p.bst_y ? 2 : 1);
+    const int stats = wino4_stats(p);
     if (stats && HAS_RES) return hipErrorInvalidValue;
     p.bn_bpg = (int)nblk;
     auto kern = stats == 2 ? conv_wino4_kernel<false, 2> : stats == 1 ? conv_wino4_kernel<false, 1> : conv_wino4_kernel<HAS_RES, 0>;
     static bool attr_done[3][64] = {};
-    if (cerb_attr_needed(attr_done[stats])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + PROF_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    long long grid = 256;  // persistent: one workgroup per CU
-    if (grid > items) grid = items;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), LDS_BYTES + PROF_BYTES, st, p);
-    return hipGetLastError();
+    return wino4_launch(kern, attr_done[stats], items, LDS_BYTES + PROF_BYTES, p, st);
 }
 
 #ifdef W4_PROF

@@ -11,21 +11,19 @@
 //   * weights: two 16-byte loads per position (every weight register feeds ONE matrix instruction: 32 bytes / clock / CU from L2, what
 //     conv_wino.hip has always drawn).
 // V tile [36][16 tiles][32 ch] = 72 KiB, double-buffered; 16-byte slots XOR-swizzled by the tile index (conflict-free ds_read_b128 /
-// ds_write_b64 without padding).  Output rows leave through the free V buffer as whole lines (conv_wino4.hip).
+// ds_write_b64 without padding).  Output rows leave through the free V buffer as whole lines (wino_common.h: wino4_store_block).
 // Reference layers: models/utils/conv_layers.py:24-60 (_ConvLayer) and models/backbone/resnet.py:81-97 (BasicBlock).
 #include <stdlib.h>
 #include <type_traits>
 
-#include "cerb_common.h"
+#include "wino_common.h"
 
 namespace {
 constexpr int NPOS = 36;
 constexpr int NT = 16;                        // tiles per item: one block of 4x4 tiles
-constexpr int BLK = 16;                       // a block is 16x16 output pixels
 constexpr int CB = 32;                        // input channels per LDS pass
 constexpr int V_FLOATS = NPOS * NT * CB;      // one V buffer: 72 KiB
 constexpr int LDS_BYTES = 2 * V_FLOATS * 4;   // double-buffered: 144 KiB
-constexpr int OPX = 68;                       // output staging: floats per pixel (64 channels + 4: bank skew)
 static_assert(256 * OPX + 16 <= V_FLOATS, "a block's outputs are staged in one V buffer");
 #ifndef W4B_RP
 #define W4B_RP 9
@@ -45,30 +43,9 @@ constexpr int BIAS_XI = 7;                    // A^T[i][1] A[1][j] = 1 for all 1
 constexpr int WAVE_W_BYTES = NPOS * 2 * 1024;     // one wave's share of a chunk: 36 positions x 2 KiB
 constexpr int CHUNK_W_BYTES = 4 * WAVE_W_BYTES;   // packed weights of one (cout block, 32-channel chunk): 288 KiB
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
-}
-// the input patch: 2 GiB of range, so that a lane offset of 0x80000000 is out of range and the hardware returns zeros (zero padding of the
-// image border without a single VALU instruction)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_lim(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef W4B_WAUX
 #define W4B_WAUX 0
 #endif
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, W4B_WAUX));
-}
-__device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff, 0);
-    asm volatile("s_nop 1");  // gfx950 store hazard, see conv_wino.hip buf_store / tests/test_isa_hazard.py
-    __builtin_amdgcn_sched_barrier(0);
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 buf_load2(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, 0));
-}
 
 #ifdef W4_PROF
 // developer instrumentation (scripts/dev_w4prof.py): wave 0 of workgroup W4_PROF stamps s_memtime at every pair-step of its second item
@@ -78,9 +55,7 @@ constexpr int PROF_BYTES = 16 * 40 * 8;
 constexpr int PROF_BYTES = 0;
 #endif
 
-struct Item {
-    int g, cb, n, by, bx;  // group, block of 64 output channels, image, block row / column inside the launch's block grid
-};
+using Item = Wino4Block;  // n: the image, or with PACKED the packed block
 }  // namespace
 
 // STATS (training forward): BatchNorm statistics partials per block from the output stage (ConvParams::bn_part; see conv_wino4.hip)
@@ -235,41 +210,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 d[P][r][q] = ok ? d[P][r][q] : z;
             }
     };
-    // B^T x for the points (0, 1, -1, 2, -2, inf), in place: 12 packed operations.  Written as v_pk_fma_f32 / v_pk_add_f32 by hand: hipcc
-    // (ROCm 7.2) scalarises vector subtractions and multiplies by negative literals (116 v_fma_f32 + 44 v_add_f32 + 64 packed instructions
-    // per chunk instead of 144 packed ones), and every VALU instruction of this wave is a matrix-pipe cycle lost (one wave per SIMD).
+    // B^T x, in place (wino_common.h: wino4_bt6), with its constants pinned in registers
     f32x2 k2 = {2.f, 2.f}, k4 = {4.f, 4.f}, k5 = {5.f, 5.f};
     asm volatile("" : "+v"(k2), "+v"(k4), "+v"(k5));
-    auto bt6 = [&](f32x2& x0, f32x2& x1, f32x2& x2, f32x2& x3, f32x2& x4, f32x2& x5) __attribute__((always_inline)) {
-#ifdef W4_C_XF
-        const f32x2 t0 = x4 - 4.f * x2, t1 = x3 - 4.f * x1;
-        const f32x2 u0 = x4 - x2, u1 = x3 - x1;
-        x0 = (4.f * x0 + x4) - 5.f * x2;
-        x5 = (4.f * x1 + x5) - 5.f * x3;
-        x1 = t0 + t1;
-        x2 = t0 - t1;
-        x3 = u0 + 2.f * u1;
-        x4 = u0 - 2.f * u1;
-#else
-        f32x2 t0, t1, u0, u1;
-        asm("v_pk_fma_f32 %6, %2, %11, %4 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t0 = x4 - 4 x2
-            "v_pk_fma_f32 %7, %1, %11, %3 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t1 = x3 - 4 x1
-            "v_pk_add_f32 %8, %4, %2 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u0 = x4 - x2
-            "v_pk_add_f32 %9, %3, %1 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u1 = x3 - x1
-            "v_pk_fma_f32 %0, %0, %11, %4\n\t"                                  // x0 = 4 x0 + x4
-            "v_pk_fma_f32 %5, %1, %11, %5\n\t"                                  // x5 = 4 x1 + x5
-            "v_pk_fma_f32 %0, %2, %12, %0 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x0 -= 5 x2
-            "v_pk_fma_f32 %5, %3, %12, %5 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x5 -= 5 x3
-            "v_pk_add_f32 %1, %6, %7\n\t"                                       // x1 = t0 + t1
-            "v_pk_add_f32 %2, %6, %7 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // x2 = t0 - t1
-            "v_pk_fma_f32 %3, %9, %10, %8\n\t"                                  // x3 = u0 + 2 u1
-            "v_pk_fma_f32 %4, %9, %10, %8 neg_lo:[1,0,0] neg_hi:[1,0,0]"         // x4 = u0 - 2 u1
-            : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "=&v"(t0), "=&v"(t1), "=&v"(u0), "=&v"(u1)
-            : "v"(k2), "v"(k4), "v"(k5));
-#endif
-    };
-    auto pass_v = [&](int P, int q) __attribute__((always_inline)) { bt6(d[P][0][q], d[P][1][q], d[P][2][q], d[P][3][q], d[P][4][q], d[P][5][q]); };  // down column q
-    auto pass_h = [&](int P, int r) __attribute__((always_inline)) { bt6(d[P][r][0], d[P][r][1], d[P][r][2], d[P][r][3], d[P][r][4], d[P][r][5]); };  // along row r
+    auto pass_v = [&](int P, int q) __attribute__((always_inline)) { wino4_bt6(d[P][0][q], d[P][1][q], d[P][2][q], d[P][3][q], d[P][4][q], d[P][5][q], k2, k4, k5); };  // down column q
+    auto pass_h = [&](int P, int r) __attribute__((always_inline)) { wino4_bt6(d[P][r][0], d[P][r][1], d[P][r][2], d[P][r][3], d[P][r][4], d[P][r][5], k2, k4, k5); };  // along row r
 #ifdef W4B_ABL_NOVW
     f32x2 abl_sink = {0.f, 0.f};
 #endif
@@ -310,14 +255,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     f32x4 wq[RP][2];
 #pragma unroll
     for (int dd = 0; dd < WDP; ++dd) {
-        wq[dd][0] = buf_load(rw, wlane, dd * 2048);
-        wq[dd][1] = buf_load(rw, wlane, dd * 2048 + 1024);
+        wq[dd][0] = buf_load<W4B_WAUX>(rw, wlane, dd * 2048);
+        wq[dd][1] = buf_load<W4B_WAUX>(rw, wlane, dd * 2048 + 1024);
     }
     f32x4 bnext;
     auto load_bias = [&](const Item& wi) {
         const float* bias = p.bias + wi.g * p.bias_gs + wi.cb * 64 + 16 * a;
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, 64, 0x00020000);
-        bnext = buf_load(rb, (unsigned)ks * 16u, 0);
+        bnext = buf_load<W4B_WAUX>(rb, (unsigned)ks * 16u, 0);
     };
     load_bias(w);
 
@@ -376,11 +321,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 for (int u = 0; u < 2; ++u) {
                     const int dd = 2 * s + u + WDP;
                     if (dd < NPOS) {
-                        wq[dd % RP][0] = buf_load(rw, wlane, wcur_off + dd * 2048);
-                        wq[dd % RP][1] = buf_load(rw, wlane, wcur_off + dd * 2048 + 1024);
+                        wq[dd % RP][0] = buf_load<W4B_WAUX>(rw, wlane, wcur_off + dd * 2048);
+                        wq[dd % RP][1] = buf_load<W4B_WAUX>(rw, wlane, wcur_off + dd * 2048 + 1024);
                     } else {
-                        wq[(dd - NPOS) % RP][0] = buf_load(rw_over, wlane, wover_off + (dd - NPOS) * 2048);
-                        wq[(dd - NPOS) % RP][1] = buf_load(rw_over, wlane, wover_off + (dd - NPOS) * 2048 + 1024);
+                        wq[(dd - NPOS) % RP][0] = buf_load<W4B_WAUX>(rw_over, wlane, wover_off + (dd - NPOS) * 2048);
+                        wq[(dd - NPOS) % RP][1] = buf_load<W4B_WAUX>(rw_over, wlane, wover_off + (dd - NPOS) * 2048 + 1024);
                     }
                 }
                 if (s + 1 < NPOS / 2) {
@@ -443,148 +388,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         load_bias(wnx);  // before this item's stores enter the in-order vmcnt queue (the next item's first WDP positions already went out)
         {
             int lane_o = lane;
-            asm volatile("" : "+v"(lane_o));  // recomputed per item: keeps these out of the MFMA phase's register budget
-            const int mo = lane_o & 15, kso = lane_o >> 4;
-            float* stg = lds + V_FLOATS;
-            // write side: lane (tile mo, channel quad kso) owns pixels (4 ty + i, 4 tx + j); pixel stride 68 floats, 4 floats of skew per tile row
-            const int sw = ((64 * (mo >> 2) + 4 * (mo & 3)) * OPX + 4 * (mo >> 2) + 16 * a + 4 * kso);
-            // read side: wave a stores pixel rows 4 a .. 4 a + 3; lane = (pixel lane_o >> 4 of a group of four, 16-byte piece lane_o & 15)
-            const int sr = ((64 * a + (lane_o >> 4)) * OPX + 4 * a + 4 * (lane_o & 15));
-            const int orow = p.Wo * p.Cout * 4, opix = p.Cout * 4;
-            const unsigned ooff = (unsigned)((((PACKED ? 0 : 4 * a * p.Wo) + (lane_o >> 4)) * p.Cout + 4 * (lane_o & 15)) * 4);
-            const float floor_ = p.relu ? 0.f : -3.402823466e38f;
-            const unsigned span = PACKED ? (unsigned)((long long)p.N * p.Ho * p.Wo * p.Cout * 4) : (unsigned)(BLK * p.Wo * p.Cout * 4);
-            const int by0 = oy0(w), bx0 = ox0(w);
-            const long long origin = PACKED ? (long long)w.cb * 64 : (((long long)w.n * p.Ho + by0) * p.Wo + bx0) * p.Cout + w.cb * 64;  // floats, uniform
-            const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(p.out + w.g * p.out_gs + origin, 0, span, 0x00020000);
-            const bool partial = !PACKED && ((by0 + BLK > p.Ho) || (bx0 + BLK > p.Wo));
-            // PACKED: this wave stores tiles 4 a .. 4 a + 3 of the item; a tile's byte offset in the group's tensor joins the lane's own offset
-            unsigned toff[4] = {0u, 0u, 0u, 0u};
-            bool tvalid[4] = {true, true, true, true};
-            if (PACKED) {
-#pragma unroll
-                for (int x4 = 0; x4 < 4; ++x4) {
-                    const int T = w.n * NT + 4 * a + x4;
-                    tvalid[x4] = T < p.pk_ntile;
-                    int n, ty, tx;
-                    pk_decode(tvalid[x4] ? T : 0, n, ty, tx);
-                    toff[x4] = (unsigned)(((n * p.Ho + 4 * ty) * p.Wo + 4 * tx) * p.Cout * 4);
-                }
-            }
-            // vertical pass: T[i][b] = sum_a A^T[i][a] M[a][b]
-            f32x4 T[4][6];
-#pragma unroll
-            for (int b = 0; b < 6; ++b) {
-                const f32x4 m0 = acc[0 * 6 + b], m1 = acc[1 * 6 + b], m2 = acc[2 * 6 + b], m3 = acc[3 * 6 + b], m4 = acc[4 * 6 + b], m5 = acc[5 * 6 + b];
-                const f32x4 s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-                T[0][b] = m0 + s1 + s2;
-                T[1][b] = d1 + 2.f * d2;
-                T[2][b] = s1 + 4.f * s2;
-                T[3][b] = (d1 + 8.f * d2) + m5;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 s1 = T[i][1] + T[i][2], d1 = T[i][1] - T[i][2], s2 = T[i][3] + T[i][4], d2 = T[i][3] - T[i][4];
-                *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 0) * OPX) = T[i][0] + s1 + s2;
-                *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 1) * OPX) = d1 + 2.f * d2;
-                *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 2) * OPX) = s1 + 4.f * s2;
-                *reinterpret_cast<f32x4*>(stg + sw + (16 * i + 3) * OPX) = (d1 + 8.f * d2) + T[i][5];
-            }
-            W4_STAMP(1);
-            __syncthreads();
-            W4_STAMP(2);
-            // 16 groups of four pixels per wave: row 4 a + (k >> 2), pixels 4 (k & 3) .. + 3
-            unsigned vo[4];
-#pragma unroll
-            for (int x4 = 0; x4 < 4; ++x4) {
-                const bool ok = PACKED ? tvalid[x4] : (!partial || (bx0 + 4 * x4 + (lane_o >> 4) < p.Wo));
-                vo[x4] = ok ? ooff + toff[x4] : 0x80000000u;  // out-of-range offsets: the hardware drops the store / returns 0
-            }
-            f32x4 res[16];
-            if (HAS_RES) {
-                const __amdgpu_buffer_rsrc_t r_res =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.resid + w.g * p.resid_gs + origin), 0, span, 0x00020000);
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                    res[k] = buf_load(r_res, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + (PACKED ? 0 : 4 * (k & 3) * opix));
-                }
-            }
-            f32x4 yv[STATS == 2 ? 16 : 1], bm, brs, bga, bbe;  // STATS 2: the BatchNorm's input at this lane's pixels, its parameters for this lane's four channels
-            if constexpr (STATS == 2) {
-                const __amdgpu_buffer_rsrc_t r_y =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bst_y + w.g * p.bst_y_gs + origin), 0, span, 0x00020000);
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                    yv[k] = buf_load(r_y, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + (PACKED ? 0 : 4 * (k & 3) * opix));
-                }
-                const int pc = w.g * p.Cout + w.cb * 64 + 4 * (lane_o & 15);
-                bm = *reinterpret_cast<const f32x4*>(p.bst_mean + pc);
-                brs = *reinterpret_cast<const f32x4*>(p.bst_rstd + pc);
-                bga = *reinterpret_cast<const f32x4*>(p.bst_gamma + pc);
-                bbe = *reinterpret_cast<const f32x4*>(p.bst_beta + pc);
-            }
-            f32x4 bts = {0.f, 0.f, 0.f, 0.f}, btq = {0.f, 0.f, 0.f, 0.f};  // STATS: this lane's 16 pixels x 4 channels
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                f32x4 o = *reinterpret_cast<const f32x4*>(stg + sr + (16 * (k >> 2) + 4 * (k & 3)) * OPX);
-                if (HAS_RES) o = o + res[k];
-                o[0] = fmaxf(o[0], floor_);
-                o[1] = fmaxf(o[1], floor_);
-                o[2] = fmaxf(o[2], floor_);
-                o[3] = fmaxf(o[3], floor_);
-                const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
-                if constexpr (STATS == 1) {
-                    if (rowok && vo[k & 3] != 0x80000000u) {
-                        bts = bts + o;
-                        btq[0] = fmaf(o[0], o[0], btq[0]);
-                        btq[1] = fmaf(o[1], o[1], btq[1]);
-                        btq[2] = fmaf(o[2], o[2], btq[2]);
-                        btq[3] = fmaf(o[3], o[3], btq[3]);
-                    }
-                }
-                if constexpr (STATS == 2) {
-                    if (rowok && vo[k & 3] != 0x80000000u) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {  // the mask by the ONE expression every BatchNorm kernel uses (train_kernels.hip: bn_out)
-                            const float yy = yv[k][e];
-                            const float z = __fmaf_rn(yy - bm[e], brs[e] * bga[e], bbe[e]);
-                            const float g = z > 0.f ? o[e] : 0.f;
-                            bts[e] += g;
-                            btq[e] = fmaf(g, (yy - bm[e]) * brs[e], btq[e]);
-                        }
-                    }
-                }
-                buf_store(o, r_out, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + (PACKED ? 0 : 4 * (k & 3) * opix));
-            }
-            if constexpr (STATS) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    bts[e] += __shfl_xor(bts[e], 16);
-                    bts[e] += __shfl_xor(bts[e], 32);
-                    btq[e] += __shfl_xor(btq[e], 16);
-                    btq[e] += __shfl_xor(btq[e], 32);
-                }
-                if (lane_o < 16) {
-                    *reinterpret_cast<f32x4*>(bnred + (a * 16 + lane_o) * 8) = bts;
-                    *reinterpret_cast<f32x4*>(bnred + (a * 16 + lane_o) * 8 + 4) = btq;
-                }
-            }
-            W4_STAMP(3);
-            __syncthreads();  // the staging buffer is V buffer 1: the next item's first chunk writes it
-            W4_STAMP(4);
-            if constexpr (STATS) {
-                if (a == 0 && lane_o < 16 && p.bn_part) {
-                    const long long blk = PACKED ? (long long)w.n : ((long long)w.n * p.tiles_y + w.by) * p.tiles_x + w.bx;
-                    double* dst = p.bn_part + (((long long)w.g * p.bn_bpg + blk) * p.Cout + w.cb * 64 + 4 * lane_o) * 2;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dst[2 * e] = (double)(((bnred[lane_o * 8 + e] + bnred[(16 + lane_o) * 8 + e]) + bnred[(32 + lane_o) * 8 + e]) + bnred[(48 + lane_o) * 8 + e]);
-                        dst[2 * e + 1] = (double)(((bnred[lane_o * 8 + 4 + e] + bnred[(16 + lane_o) * 8 + 4 + e]) + bnred[(32 + lane_o) * 8 + 4 + e]) + bnred[(48 + lane_o) * 8 + 4 + e]);
-                    }
-                }
-            }
+            asm volatile("" : "+v"(lane_o));  // recomputed per item: keeps what derives from it out of the MFMA phase's register budget
+            wino4_store_block<HAS_RES, STATS, PACKED, W4B_WAUX, 0>(
+                p, lds + V_FLOATS, bnred, a, lane_o, w, false, [&](int xi) __attribute__((always_inline)) -> const f32x4& { return acc[xi]; }, pk_decode,
+                [&](int k) __attribute__((always_inline)) { if (k) W4_STAMP(k); });
         }
 #ifdef W4_PROF
         if (prof_on) {
@@ -619,36 +426,21 @@ int cerb_wino4b_bn_blocks(const ConvParams& p) {
 
 template <bool HAS_RES>
 static hipError_t launch_wino4b(ConvParams p, hipStream_t st) {
-    p.tiles_x = (p.Wo + BLK - 1) / BLK;  // blocks, not tiles
-    p.tiles_y = (p.Ho + BLK - 1) / BLK;
-    p.ty_off = p.tx_off = 0;
-    if (p.roi_y1 > p.roi_y0 && p.roi_x1 > p.roi_x0) {
-        p.ty_off = p.roi_y0 / BLK;
-        p.tx_off = p.roi_x0 / BLK;
-        p.tiles_y = (p.roi_y1 + BLK - 1) / BLK - p.ty_off;
-        p.tiles_x = (p.roi_x1 + BLK - 1) / BLK - p.tx_off;
-    }
+    const long long nblk = wino4_block_grid(p);
     const bool packed = cerb_wino4b_packed(p);
     if (packed) {
         p.pk_ty = p.Ho / 4;
         p.pk_tx = p.Wo / 4;
         p.pk_ntile = p.N * p.pk_ty * p.pk_tx;
     }
-    const long long items = packed ? (long long)p.groups * ((p.pk_ntile + NT - 1) / NT) * (p.Cout / 64) : (long long)p.groups * p.N * p.tiles_x * p.tiles_y * (p.Cout / 64);
-    const int stats = p.bn_part == nullptr ? 0 : (p.bst_y ? 2 : 1);
+    const long long items = packed ? (long long)p.groups * ((p.pk_ntile + NT - 1) / NT) * (p.Cout / 64) : p.groups * nblk * (p.Cout / 64);
+    const int stats = wino4_stats(p);
     if (stats && HAS_RES) return hipErrorInvalidValue;
-    p.bn_bpg = packed ? cerb_wino4b_bn_blocks(p) : p.N * p.tiles_x * p.tiles_y;
+    p.bn_bpg = packed ? cerb_wino4b_bn_blocks(p) : (int)nblk;
     auto kern = packed ? (stats == 2 ? conv_wino4b_kernel<false, 2, true> : stats == 1 ? conv_wino4b_kernel<false, 1, true> : conv_wino4b_kernel<HAS_RES, 0, true>)
                        : (stats == 2 ? conv_wino4b_kernel<false, 2, false> : stats == 1 ? conv_wino4b_kernel<false, 1, false> : conv_wino4b_kernel<HAS_RES, 0, false>);
     static bool attr_done[6][64] = {};
-    if (cerb_attr_needed(attr_done[stats + (packed ? 3 : 0)])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + PROF_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    long long grid = 256;  // persistent: one workgroup per CU
-    if (grid > items) grid = items;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), LDS_BYTES + PROF_BYTES, st, p);
-    return hipGetLastError();
+    return wino4_launch(kern, attr_done[stats + (packed ? 3 : 0)], items, LDS_BYTES + PROF_BYTES, p, st);
 }
 
 #ifdef W4_PROF

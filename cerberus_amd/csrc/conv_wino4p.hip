@@ -14,12 +14,11 @@
 // Reference layers: models/utils/conv_layers.py:24-60 (_ConvLayer) inside models/net_desc.py:182-198 (the decoder loop).
 #include <type_traits>
 
-#include "cerb_common.h"
+#include "wino_common.h"
 
 namespace {
 constexpr int NPOS = 36;
 constexpr int NT = 32;                        // tiles per item: two blocks of 4x4 tiles
-constexpr int BLK = 16;                       // a block is 16x16 output pixels
 constexpr int CB = 16;                        // input channels per LDS pass = one plane
 constexpr int V_FLOATS = NPOS * NT * CB;      // one V buffer: 72 KiB
 constexpr int LDS_BYTES = 2 * V_FLOATS * 4;   // double-buffered: 144 KiB
@@ -96,29 +95,12 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, -1, 0x00020000);
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #ifndef P4_WAUX
 #define P4_WAUX 0
 #endif
 #ifndef P4_PAUX
 #define P4_PAUX 0
 #endif
-__device__ __forceinline__ f32x4 buf_load(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, P4_WAUX));
-}
-__device__ __forceinline__ void buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)voff, soff, 0);
-    asm volatile("s_nop 1");  // gfx950 store hazard, see conv_wino.hip buf_store / tests/test_isa_hazard.py
-    __builtin_amdgcn_sched_barrier(0);
-}
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 buf_load2(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, soff, P4_PAUX));
-}
 
 // The matrix instruction, with the accumulator's register file chosen by the caller.  hipcc does not model what is inside the string:
 // the operands' s_waitcnt are still its own (they are ordinary register uses), the wait states are ours -- an accumulate chain needs
@@ -300,7 +282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #ifdef P4_ABL_PREVADD
         if ((rr == 0 || rr == 1 || rr == 3 || rr == 5) && (qq == 0 || qq == 1 || qq == 3 || qq == 5))
             pv[rr == 0 ? 0 : rr == 1 ? 1 : rr == 3 ? 2 : 3][qq == 0 ? 0 : qq == 1 ? 1 : qq == 3 ? 2 : 3] =
-                buf_load2(r, poff[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + ((ii ^ 1) * 4 + (jj ^ 2)) * 1024);
+                buf_load2<P4_PAUX>(r, poff[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + ((ii ^ 1) * 4 + (jj ^ 2)) * 1024);
 #endif
 #ifdef P4_ABL_LDSPATCH  // ablation (round 4): what an LDS-staged raw patch would cost -- the thread reads its 36 pixels from LDS
         // (any in-range address: the values are garbage) and the workgroup's unique pixels arrive through stage_lds() below
@@ -314,34 +296,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if (rr == 0 || rr == 5 || qq == 0 || qq == 5) return;
 #endif
 #ifdef P4_ABL_HALOOWN   // ablation: every halo pixel is read from the lane's OWN tile (same instruction count, no lane leaves the block or its tile's row)
-        d[rr][qq] = buf_load2(r, poff[1][1], chunk_off + (ii * 4 + jj) * 1024);
+        d[rr][qq] = buf_load2<P4_PAUX>(r, poff[1][1], chunk_off + (ii * 4 + jj) * 1024);
         return;
 #endif
 #ifdef P4_ABL_CORNEROWN
-        if ((rr == 0 || rr == 5) && (qq == 0 || qq == 5)) { d[rr][qq] = buf_load2(r, poff[1][1], chunk_off + (ii * 4 + jj) * 1024); return; }
+        if ((rr == 0 || rr == 5) && (qq == 0 || qq == 5)) { d[rr][qq] = buf_load2<P4_PAUX>(r, poff[1][1], chunk_off + (ii * 4 + jj) * 1024); return; }
 #endif
-        d[rr][qq] = buf_load2(r, poff[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + (ii * 4 + jj) * 1024);
+        d[rr][qq] = buf_load2<P4_PAUX>(r, poff[rr == 0 ? 0 : rr == 5 ? 2 : 1][qq == 0 ? 0 : qq == 5 ? 2 : 1], chunk_off + (ii * 4 + jj) * 1024);
     };
-    // B^T x for the points (0, 1, -1, 2, -2, inf), in place: 12 packed operations (conv_wino4.hip: written by hand, hipcc scalarises them)
+    // B^T x, in place (wino_common.h: wino4_bt6), with its constants pinned in registers
     f32x2 k2 = {2.f, 2.f}, k4 = {4.f, 4.f}, k5 = {5.f, 5.f};
     asm volatile("" : "+v"(k2), "+v"(k4), "+v"(k5));
-    auto bt6 = [&](f32x2& x0, f32x2& x1, f32x2& x2, f32x2& x3, f32x2& x4, f32x2& x5) __attribute__((always_inline)) {
-        f32x2 t0, t1, u0, u1;
-        asm("v_pk_fma_f32 %6, %2, %11, %4 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t0 = x4 - 4 x2
-            "v_pk_fma_f32 %7, %1, %11, %3 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // t1 = x3 - 4 x1
-            "v_pk_add_f32 %8, %4, %2 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u0 = x4 - x2
-            "v_pk_add_f32 %9, %3, %1 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // u1 = x3 - x1
-            "v_pk_fma_f32 %0, %0, %11, %4\n\t"                                  // x0 = 4 x0 + x4
-            "v_pk_fma_f32 %5, %1, %11, %5\n\t"                                  // x5 = 4 x1 + x5
-            "v_pk_fma_f32 %0, %2, %12, %0 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x0 -= 5 x2
-            "v_pk_fma_f32 %5, %3, %12, %5 neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"   // x5 -= 5 x3
-            "v_pk_add_f32 %1, %6, %7\n\t"                                       // x1 = t0 + t1
-            "v_pk_add_f32 %2, %6, %7 neg_lo:[0,1] neg_hi:[0,1]\n\t"            // x2 = t0 - t1
-            "v_pk_fma_f32 %3, %9, %10, %8\n\t"                                  // x3 = u0 + 2 u1
-            "v_pk_fma_f32 %4, %9, %10, %8 neg_lo:[1,0,0] neg_hi:[1,0,0]"         // x4 = u0 - 2 u1
-            : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "=&v"(t0), "=&v"(t1), "=&v"(u0), "=&v"(u1)
-            : "v"(k2), "v"(k4), "v"(k5));
-    };
 #if defined(P4_ABL_PREVADD) && P4_ABL_PREVADD + 0 == 2
     // ... and the bilinear blend itself (the decoder entry is align_corners = False bilinear, net_kernels.hip: blend2 = fma(a, x, b * y)): per patch column
     // four horizontal blends of the 4 x 4 source pixels, six vertical ones, six adds -- 26 packed operations x 6 columns beside the input transform's 144
@@ -367,7 +332,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[3][q]) : "v"(v3));
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[4][q]) : "v"(v4));
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[5][q]) : "v"(v5));
-        bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q]);
+        wino4_bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q], k2, k4, k5);
     };
 #elif defined(P4_ABL_PREVADD)
     auto pass_v = [&](int q) __attribute__((always_inline)) {
@@ -378,12 +343,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[3][q]) : "v"(pv[2][qi]));
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[4][q]) : "v"(pv[2][qi]));
         asm("v_pk_add_f32 %0, %0, %1" : "+v"(d[5][q]) : "v"(pv[3][qi]));
-        bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q]);
+        wino4_bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q], k2, k4, k5);
     };
 #else
-    auto pass_v = [&](int q) __attribute__((always_inline)) { bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q]); };  // down column q
+    auto pass_v = [&](int q) __attribute__((always_inline)) { wino4_bt6(d[0][q], d[1][q], d[2][q], d[3][q], d[4][q], d[5][q], k2, k4, k5); };  // down column q
 #endif
-    auto pass_h = [&](int r) __attribute__((always_inline)) { bt6(d[r][0], d[r][1], d[r][2], d[r][3], d[r][4], d[r][5]); };  // along row r
+    auto pass_h = [&](int r) __attribute__((always_inline)) { wino4_bt6(d[r][0], d[r][1], d[r][2], d[r][3], d[r][4], d[r][5], k2, k4, k5); };  // along row r
     auto write_row = [&](int buf, int r) __attribute__((always_inline)) {
 #pragma unroll
         for (int b = 0; b < 6; ++b) *reinterpret_cast<f32x2*>(lds + buf * V_FLOATS + (r * 6 + b) * NT * CB + vw) = d[r][b];
@@ -417,12 +382,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // lives in slot q % RING.  Steps past the chunk's 36 belong to the next chunk, or to the next item's first chunk.
     f32x4 wq[RING];
 #pragma unroll
-    for (int dd = 0; dd < PRE; ++dd) wq[dd] = buf_load(rw, wlane, dd * 1024);
+    for (int dd = 0; dd < PRE; ++dd) wq[dd] = buf_load<P4_WAUX>(rw, wlane, dd * 1024);
     f32x4 bnext;
     auto load_bias = [&](const Item& wi) {
         const float* bias = p.bias + wi.g * p.bias_gs + wi.cb * 64 + 16 * a;
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias), 0, 64, 0x00020000);
-        bnext = buf_load(rb, (unsigned)(fresh_lane() >> 4) * 16u, 0);
+        bnext = buf_load<P4_WAUX>(rb, (unsigned)(fresh_lane() >> 4) * 16u, 0);
     };
     load_bias(w);
 
@@ -484,8 +449,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                     for (int dd = q + WD; dd < q + WD + WB; ++dd) {
                         if (FIRST && dd < PRE) continue;  // requested before the previous item's stores (or in the prologue)
-                        if (dd < NS) wq[dd % RING] = buf_load(rw, wlane, wcur_off + dd * 1024);
-                        else wq[(dd - NS) % RING] = buf_load(rw_over, wlane, wover_off + (dd - NS) * 1024);
+                        if (dd < NS) wq[dd % RING] = buf_load<P4_WAUX>(rw, wlane, wcur_off + dd * 1024);
+                        else wq[(dd - NS) % RING] = buf_load<P4_WAUX>(rw_over, wlane, wover_off + (dd - NS) * 1024);
                     }
                 }
 #endif
@@ -534,8 +499,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                     for (int dd = q + WD; dd < q + WD + WB; ++dd) {
                         if (FIRST && dd < PRE) continue;  // requested before the previous item's stores (or in the prologue)
-                        if (dd < NS) wq[dd % RING] = buf_load(rw, wlane, wcur_off + dd * 1024);
-                        else wq[(dd - NS) % RING] = buf_load(rw_over, wlane, wover_off + (dd - NS) * 1024);
+                        if (dd < NS) wq[dd % RING] = buf_load<P4_WAUX>(rw, wlane, wcur_off + dd * 1024);
+                        else wq[(dd - NS) % RING] = buf_load<P4_WAUX>(rw_over, wlane, wover_off + (dd - NS) * 1024);
                     }
                 }
 #endif
@@ -591,7 +556,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // vmcnt retires in order across loads AND stores: everything the next item needs during its first PRE steps is requested here, before
         // this item's stores enter the queue (its steps 0 .. WD-1 went out during the last chunk).
 #pragma unroll
-        for (int dd = WD; dd < PRE; ++dd) wq[dd % RING] = buf_load(rw_nx, wlane, dd * 1024);
+        for (int dd = WD; dd < PRE; ++dd) wq[dd % RING] = buf_load<P4_WAUX>(rw_nx, wlane, dd * 1024);
         load_bias(wnx);
         P4_STAMP(15, 0);
         wait_mfma_results();
@@ -682,28 +647,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 hipError_t cerb_launch_wino4p(ConvParams p, hipStream_t st) {
     if (p.Cin % CB || p.Cout % 64 || p.resid || p.pl_byp < 3 || p.pl_bxp < 3 || p.H != p.Ho || p.W != p.Wo) return hipErrorInvalidValue;
-    p.tiles_x = (p.Wo + BLK - 1) / BLK;  // blocks, not tiles
-    p.tiles_y = (p.Ho + BLK - 1) / BLK;
-    p.ty_off = p.tx_off = 0;
-    if (p.roi_y1 > p.roi_y0 && p.roi_x1 > p.roi_x0) {
-        p.ty_off = p.roi_y0 / BLK;
-        p.tx_off = p.roi_x0 / BLK;
-        p.tiles_y = (p.roi_y1 + BLK - 1) / BLK - p.ty_off;
-        p.tiles_x = (p.roi_x1 + BLK - 1) / BLK - p.tx_off;
-    }
+    const long long nblk = wino4_block_grid(p);
     if (p.pl_byp != (p.Ho + BLK - 1) / BLK + 2 || p.pl_bxp != (p.Wo + BLK - 1) / BLK + 2) return hipErrorInvalidValue;
-    const long long nblk = (long long)p.N * p.tiles_x * p.tiles_y;
     const long long items = (long long)p.groups * ((nblk + 1) / 2) * (p.Cout / 64);
     auto kern = p.level_tag ? conv_wino4p_kernel<1> : conv_wino4p_kernel<0>;
     static bool attr_done[2][64] = {};
-    if (cerb_attr_needed(attr_done[p.level_tag ? 1 : 0])) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES + PROF_BYTES);
-        if (e != hipSuccess) return e;
-    }
-    long long grid = 256;  // persistent: one workgroup per CU
-    if (grid > items) grid = items;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), LDS_BYTES + PROF_BYTES, st, p);
-    return hipGetLastError();
+    return wino4_launch(kern, attr_done[p.level_tag ? 1 : 0], items, LDS_BYTES + PROF_BYTES, p, st);
 }
 
 #ifdef P4_PROF
