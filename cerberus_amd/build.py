@@ -21,6 +21,9 @@ SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip
 # (every one folds to its default); the same units compiled with -DCERB_DEV_SWITCHES, linked with the other units' objects, make
 # libcerberus_hip_dev.so -- loaded only by the A/B tests' child processes (CERB_DEV_LIB=1, cerberus_amd/_lib.py).
 DEV_SOURCES = ["cerb_api.hip", "cerb_train.hip", "postproc.hip", "conv_wino4b.hip", "train_kernels.hip"]
+# Linked into libcerberus_hip_dev.so ONLY: the test-only entry layer (cerb_dev_* wrappers over single launchers of cerb_net.h, for tests/dev_kernels.py).
+# The product library neither compiles nor exports them (tests/test_abi.py).
+DEV_ONLY_SOURCES = ["dev_entry.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 # conv_wino4.hip: the 36-step chunk (288 matrix instructions) must be fully unrolled for its 288 accumulators to be registers (the default
 # pragma-unroll budget is 16 k instructions); the matrix instructions start in VGPR form and the register allocator moves the ones that do
@@ -75,6 +78,15 @@ def build(force=False, verbose=True):
             continue
         obj = os.path.join(CSRC, "dev_" + src.replace(".hip", ".o"))
         dev_objs[dev_objs.index(os.path.join(CSRC, src.replace(".hip", ".o")))] = obj
+        if force or _stale(obj, [sp] + headers):
+            cmd = [hipcc] + FLAGS + ["-DCERB_DEV_SWITCHES"] + EXTRA_FLAGS.get(src, []) + ["-c", sp, "-o", obj]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            procs.append((src + " (dev)", subprocess.Popen(cmd)))
+    for src in DEV_ONLY_SOURCES:
+        sp = os.path.join(CSRC, src)
+        obj = os.path.join(CSRC, "dev_" + src.replace(".hip", ".o"))
+        dev_objs.append(obj)
         if force or _stale(obj, [sp] + headers):
             cmd = [hipcc] + FLAGS + ["-DCERB_DEV_SWITCHES"] + EXTRA_FLAGS.get(src, []) + ["-c", sp, "-o", obj]
             if verbose:

@@ -968,7 +968,8 @@ extern "C" int cerb_adam_step_multi(int count, float* const* param, const float*
                                     const long long* numel, float lr, float beta1, float beta2, float eps, int step, void* hip_stream) {
     if (count < 0 || (count && (!param || !grad || !exp_avg || !exp_avg_sq || !numel)) || step < 1) return fail("cerb_adam_step_multi: bad arguments");
     for (int i = 0; i < count; ++i)
-        if (!param[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] < 0) return fail("cerb_adam_step_multi: null tensor in the list");
+        if (numel[i] < 0 || (numel[i] > 0 && (!param[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i])))  // (an EMPTY tensor has no storage: its pointers may be null)
+            return fail("cerb_adam_step_multi: null tensor in the list");
     HIP_OK(cerb_launch_adam_multi(count, param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, step, (hipStream_t)hip_stream));
     return 0;
 }

@@ -1,0 +1,134 @@
+// dev_entry.hip -- test-only entry layer, linked into libcerberus_hip_dev.so ONLY (cerberus_amd/build.py: DEV_ONLY_SOURCES).  The backward kernels of
+// the training step are reachable in the product only through cerb_net_train_grads; these thin wrappers let tests/test_kernel_parity_gpu.py call one
+// launcher of cerb_net.h at a time, on raw device pointers, and compare it with a float64 reference of the same operation (tests/kernel_refs.py).
+// No logic beyond argument checks: every wrapper returns the launcher's hipError_t as an int (0 = hipSuccess, 1 = hipErrorInvalidValue for a bad
+// argument).  Not part of the boundary: include/cerberus_hip.h declares none of this and libcerberus_hip.so exports none of it (tests/test_abi.py).
+#include "cerb_net.h"
+
+#define DEV_NEED(cond) \
+    do {               \
+        if (!(cond)) return (int)hipErrorInvalidValue; \
+    } while (0)
+
+extern "C" {
+
+// ---- Winograd-domain weight gradient (conv_wgrad_wino.hip) ----------------------------------------------------------------------------------------
+int cerb_dev_wgrad_wino_supported(int H, int W, int Cin, int Cout) { return cerb_wgrad_wino_supported(H, W, Cin, Cout) ? 1 : 0; }
+size_t cerb_dev_wgrad_wino_workspace_bytes(int G, int N, int H, int W, int Cin, int Cout) {
+    return cerb_wgrad_wino_supported(H, W, Cin, Cout) ? cerb_wgrad_wino_workspace_bytes(G, N, H, W, Cin, Cout) : 0;
+}
+int cerb_dev_wgrad_wino(const float* x, const float* dy, float* dw, float* db, int G, int N, int H, int W, int Cin, int Cout, long long x_gs, void* ws, void* st) {
+    DEV_NEED(x && dy && dw && ws && G > 0 && N > 0);
+    return (int)cerb_launch_wgrad_wino(x, dy, dw, G, N, H, W, Cin, Cout, x_gs, ws, (hipStream_t)st, db);
+}
+
+// ---- direct weight gradient (conv_wgrad.hip); Ho / Wo are the OUTPUT map of the convolution ------------------------------------------------------
+size_t cerb_dev_wgrad_workspace_bytes(int G, int N, int Ho, int Wo, int Cin, int Cout, int ks, int* slices_out) {
+    return cerb_wgrad_workspace_bytes(G, N, Ho, Wo, Cin, Cout, ks, slices_out);
+}
+int cerb_dev_wgrad(const float* x, const float* dy, float* dw, float* db, int G, int N, int H, int W, int Cin, int Cout, int ks, int stride, long long x_gs, void* ws,
+                   void* st) {
+    DEV_NEED(x && dy && dw && ws && G > 0 && N > 0 && H > 0 && W > 0);
+    return (int)cerb_launch_wgrad(x, dy, dw, G, N, H, W, Cin, Cout, ks, stride, x_gs, ws, (hipStream_t)st, db);
+}
+
+// ---- the 7x7 stem on uint8 tiles ---------------------------------------------------------------------------------------------------------------
+size_t cerb_dev_stem_wgrad_mfma_workspace_bytes() { return cerb_stem_wgrad_workspace_bytes(); }
+int cerb_dev_stem_wgrad_mfma(const unsigned char* tiles, const float* dy, float* dw, int N, int H, int W, void* ws, void* st) {
+    DEV_NEED(tiles && dy && dw && ws && N > 0 && H > 0 && W > 0);
+    return (int)cerb_launch_stem_wgrad_mfma(tiles, dy, dw, N, H, W, ws, (hipStream_t)st);
+}
+int cerb_dev_stem_wgrad(const unsigned char* tiles, const float* dy, float* dw, int N, int H, int W, void* st) {
+    DEV_NEED(tiles && dy && dw && N > 0 && H > 0 && W > 0);
+    return (int)cerb_launch_stem_wgrad(tiles, dy, dw, N, H, W, (hipStream_t)st);
+}
+
+// ---- gather-form convolution backward (the fallback behind conv_algo 0): dx accumulated, dw / db assigned; any of the three may be null ---------
+int cerb_dev_conv_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* db, int G, int N, int H, int W, int Cin, int Cout, int ks, int stride,
+                      long long x_gs, void* st) {
+    DEV_NEED(dy && (dx || dw || db) && (!dx || w) && (!dw || x) && G > 0 && N > 0 && (ks == 1 || ks == 3) && (stride == 1 || stride == 2));
+    return (int)cerb_launch_conv_bwd(x, dy, w, dx, dw, db, G, N, H, W, Cin, Cout, ks, stride, x_gs, (hipStream_t)st);
+}
+
+// ---- BatchNorm: statistics, finalise from partials, backward -----------------------------------------------------------------------------------
+size_t cerb_dev_bn_workspace_bytes(int groups, long long rows, int C) { return cerb_bn_workspace_bytes(groups, rows, C); }
+size_t cerb_dev_bn_fold_workspace_bytes(int groups, int C) { return cerb_bn_fold_workspace_bytes(groups, C); }
+int cerb_dev_bn_stats(const float* x, long long group_stride, long long rows, int C, int groups, float eps, float* mean, float* rstd, float* var_unbiased, void* ws,
+                      void* st) {
+    DEV_NEED(x && mean && rstd && ws && rows > 0 && groups > 0);
+    return (int)cerb_launch_bn_stats(x, group_stride, rows, C, groups, eps, mean, rstd, var_unbiased, ws, (hipStream_t)st);
+}
+int cerb_dev_bn_finalize(const double* partial, int blocks, long long rows, int C, float eps, float* mean, float* rstd, float* var_unbiased, int groups, void* fold_ws,
+                         void* st) {
+    DEV_NEED(partial && mean && rstd && blocks > 0 && rows > 0 && groups > 0);
+    return (int)cerb_launch_bn_finalize(partial, blocks, rows, C, eps, mean, rstd, var_unbiased, (hipStream_t)st, groups, fold_ws);
+}
+int cerb_dev_bn_bwd(const float* dz, const float* z, const float* y, float* dy, float* dresid, long long group_stride, long long rows, int C, int groups, const float* mean,
+                    const float* rstd, const float* gamma, const float* beta, float* dgamma, float* dbeta, int relu, int dy_assign, int dresid_assign,
+                    unsigned long long eval_mask, void* ws, void* st) {
+    DEV_NEED(dz && y && dy && mean && rstd && gamma && dgamma && dbeta && ws && rows > 0 && groups > 0 && (!relu || z || (beta && !dresid)));
+    return (int)cerb_launch_bn_bwd(dz, z, y, dy, dresid, group_stride, rows, C, groups, mean, rstd, gamma, beta, dgamma, dbeta, relu, dy_assign, ws, (hipStream_t)st, eval_mask,
+                                   dresid_assign);
+}
+
+// ---- decoder entry: out_g = skip + up2(prev_g) ---------------------------------------------------------------------------------------------------
+int cerb_dev_upadd_bwd_fused_ok(int H, int W, int C, int G) { return cerb_upadd_bwd_fused_ok(H, W, C, G) ? 1 : 0; }
+int cerb_dev_upadd_bwd(const float* dout, float* dskip, float* dprev, int G, int N, int H, int W, int C, long long prev_gs, int shared_prev, unsigned group_mask,
+                       int skip_assign, int prev_assign, void* st) {
+    DEV_NEED(dout && dskip && dprev && G > 0 && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0);
+    return (int)cerb_launch_upadd_bwd(dout, dskip, dprev, G, N, H, W, C, prev_gs, shared_prev, (hipStream_t)st, group_mask, skip_assign, prev_assign);
+}
+
+// ---- max-pool 3x3 / 2 / 1 ------------------------------------------------------------------------------------------------------------------------
+int cerb_dev_maxpool_idx(const float* in, float* out, unsigned* idx, int N, int H, int W, int C, void* st) {
+    DEV_NEED(in && out && idx && N > 0 && H > 0 && W > 0 && C % 4 == 0);
+    return (int)cerb_launch_maxpool_idx(in, out, idx, N, H, W, C, (hipStream_t)st);
+}
+int cerb_dev_maxpool_bwd_idx(const unsigned* idx, const float* dy, float* dx, int N, int H, int W, int C, void* st) {
+    DEV_NEED(idx && dy && dx && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0);
+    return (int)cerb_launch_maxpool_bwd_idx(idx, dy, dx, N, H, W, C, (hipStream_t)st);
+}
+int cerb_dev_maxpool_bwd(const float* x, const float* ypool, const float* dy, float* dx, int N, int H, int W, int C, void* st) {
+    DEV_NEED(x && ypool && dy && dx && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0);
+    return (int)cerb_launch_maxpool_bwd(x, ypool, dy, dx, N, H, W, C, (hipStream_t)st);
+}
+
+// ---- pointwise layers -----------------------------------------------------------------------------------------------------------------------------
+int cerb_dev_pointwise_bwd(const float* x, const float* dy, const float* w, float* dx, float* dw, float* db, long long rows, int cin, int cout, const float* in_scale,
+                           int dx_assign, void* st) {
+    DEV_NEED(dy && (dx || dw || db) && (!dx || w) && (!dw || x) && rows > 0 && cin > 0 && cout > 0);
+    return (int)cerb_launch_pointwise_bwd(x, dy, w, dx, dw, db, rows, cin, cout, in_scale, dx_assign, (hipStream_t)st);
+}
+size_t cerb_dev_pw_bwd_small_workspace_bytes(long long rows, int cin, int cout) { return cerb_pw_bwd_small_workspace_bytes(rows, cin, cout); }
+int cerb_dev_pw_bwd_small(const float* x, const float* dy, const float* w, float* dx, float* dw, float* db, long long rows, int cin, int cout, int dx_assign, void* ws,
+                          void* st) {
+    DEV_NEED(x && dy && w && ws && rows > 0 && cin > 0 && cout > 0);
+    return (int)cerb_launch_pw_bwd_small(x, dy, w, dx, dw, db, rows, cin, cout, dx_assign, ws, (hipStream_t)st);
+}
+size_t cerb_dev_pw_wgrad_small_workspace_bytes(long long rows, int cin, int cout) { return cerb_pw_wgrad_small_workspace_bytes(rows, cin, cout); }
+int cerb_dev_pw_wgrad_small(const float* x, const float* dy, float* dw, long long rows, int cin, int cout, void* ws, void* st) {
+    DEV_NEED(x && dy && dw && ws && rows > 0 && cin > 0 && cout > 0);
+    return (int)cerb_launch_pw_wgrad_small(x, dy, dw, rows, cin, cout, ws, (hipStream_t)st);
+}
+
+// ---- column sums, centre crop + average pool, stride-2 dilation --------------------------------------------------------------------------------
+// (the schedule hands cerb_launch_colsum its large shared workspace; the launcher uses [G][slabs <= 2048][C] floats of it)
+size_t cerb_dev_colsum_workspace_bytes(int C, int G) { return (size_t)G * 2048 * C * 4; }
+int cerb_dev_colsum(const float* d, long long group_stride, long long rows, int C, int G, float* out, void* ws, void* st) {
+    DEV_NEED(d && out && ws && rows > 0 && C > 0 && G > 0);
+    return (int)cerb_launch_colsum(d, group_stride, rows, C, G, out, ws, (hipStream_t)st);
+}
+int cerb_dev_crop_gap(const float* x, int N, int H, int W, int C, int y0, int ch, int x0, int cw, float* out, void* st) {
+    DEV_NEED(x && out && N > 0 && C > 0 && y0 >= 0 && x0 >= 0 && ch > 0 && cw > 0 && y0 + ch <= H && x0 + cw <= W);
+    return (int)cerb_launch_crop_gap(x, N, H, W, C, y0, ch, x0, cw, out, (hipStream_t)st);
+}
+int cerb_dev_crop_gap_bwd(const float* dg, float* dx, int N, int H, int W, int C, int y0, int ch, int x0, int cw, void* st) {
+    DEV_NEED(dg && dx && N > 0 && C > 0 && y0 >= 0 && x0 >= 0 && ch > 0 && cw > 0 && y0 + ch <= H && x0 + cw <= W);
+    return (int)cerb_launch_crop_gap_bwd(dg, dx, N, H, W, C, y0, ch, x0, cw, (hipStream_t)st);
+}
+int cerb_dev_dilate2(const float* dy, float* d, long long n, int H, int W, int C, void* st) {
+    DEV_NEED(dy && d && n > 0 && H > 0 && W > 0);
+    return (int)cerb_launch_dilate2(dy, d, n, H, W, C, (hipStream_t)st);
+}
+
+}  // extern "C"

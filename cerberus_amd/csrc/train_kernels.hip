@@ -11,6 +11,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -1240,12 +1243,22 @@ __global__ void crop_gap_bwd_kernel(const float* __restrict__ dg, float* __restr
     }
 }
 // Adam (torch.optim.Adam, no weight decay / amsgrad; models/opt.py:47-58): one launch per parameter tensor in this first version
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float lr, float b1,
-                            float b2, float eps, float bc1, float bc2) {
+// bc1 / bc2 = 1 - beta^step: rounded ONCE from the host's double values (AdamCoef below), as torch rounds its Python-float scalars.  The two moment
+// recurrences run in double with double beta and 1 - beta, so each stored moment is the correctly rounded value of its recurrence: in float, 0.9f alone is
+// 2.6e-8 (relative) off and that compounds with every step a gradient stays in exp_avg (1.7e-7 against torch float64 after 8 steps, ten times torch
+// float32's own error, whose lerp never multiplies by beta1).  The kernel moves 28 bytes per element; ten double operations hide behind that.
+__device__ __forceinline__ void adam_moments(float gi, float& mi, float& vi, double b1, double b2, double omb1, double omb2) {
+    const double gd = (double)gi;
+    mi = (float)(b1 * (double)mi + omb1 * gd);
+    vi = (float)(b2 * (double)vi + omb2 * gd * gd);
+}
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long long n, float lr, float eps,
+                            float bc1, float bc2, double b1, double b2, double omb1, double omb2) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = m[i] = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = v[i] = b2 * v[i] + (1.f - b2) * gi * gi;
+        float mi = m[i], vi = v[i];
+        adam_moments(g[i], mi, vi, b1, b2, omb1, omb2);
+        m[i] = mi;
+        v[i] = vi;
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
         p[i] -= (lr / bc1) * (mi / denom);
     }
@@ -1259,15 +1272,16 @@ struct AdamTensor {
     long long n;
 };
 constexpr int ADAM_CHUNK = 16384;
-__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTensor* __restrict__ tensors, const int2* __restrict__ chunks, float lr, float b1, float b2,
-                                                         float eps, float bc1, float bc2) {
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTensor* __restrict__ tensors, const int2* __restrict__ chunks, float lr, float eps, float bc1,
+                                                         float bc2, double b1, double b2, double omb1, double omb2) {
     const int2 c = chunks[blockIdx.x];
     const AdamTensor t = tensors[c.x];
     const long long lo = (long long)c.y * ADAM_CHUNK, hi = min(t.n, lo + ADAM_CHUNK);
     for (long long i = lo + threadIdx.x; i < hi; i += 256) {
-        const float gi = t.g[i];
-        const float mi = t.m[i] = b1 * t.m[i] + (1.f - b1) * gi;
-        const float vi = t.v[i] = b2 * t.v[i] + (1.f - b2) * gi * gi;
+        float mi = t.m[i], vi = t.v[i];
+        adam_moments(t.g[i], mi, vi, b1, b2, omb1, omb2);
+        t.m[i] = mi;
+        t.v[i] = vi;
         const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
         t.p[i] -= (lr / bc1) * (mi / denom);
     }
@@ -1442,6 +1456,24 @@ hipError_t cerb_launch_copy_multi(int count, float* const* dst, const float* con
     hipLaunchKernelGGL(copy_multi_kernel, dim3((unsigned)ch.size()), dim3(256), 0, st, (const CopyDesc*)*dev_tab, (const int2*)((const char*)*dev_tab + tb));
     return hipGetLastError();
 }
+// The coefficients of one Adam step, in double on the host.  The boundary carries beta1 / beta2 as floats: 0.999f is 0.99900001287, so 1.f - 0.999f =
+// 9.99987e-4 put exp_avg_sq 1.3e-5 (relative) away from torch's, whose float kernels get float(1 - 0.999); and 1.f - powf(b, step) loses up to
+// 5e-6 (relative) of the bias corrections at small steps.  A hyperparameter that was a short decimal before it was narrowed is recovered as one (the
+// shortest decimal that rounds to the same float -- what printing a float does); any other value is taken as the float it is.
+struct AdamCoef {
+    float bc1, bc2;
+    double b1, b2, omb1, omb2;
+};
+static double adam_widen(float f) {
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.6g", (double)f);
+    const double d = strtod(buf, nullptr);
+    return (float)d == f ? d : (double)f;
+}
+static AdamCoef adam_coef(float b1, float b2, int step) {
+    const double d1 = adam_widen(b1), d2 = adam_widen(b2);
+    return AdamCoef{(float)(1.0 - pow(d1, (double)step)), (float)(1.0 - pow(d2, (double)step)), d1, d2, 1.0 - d1, 1.0 - d2};
+}
 // tables live in one device buffer that grows on demand and is reused by later steps (single optimiser stream assumed, as torch's own)
 hipError_t cerb_launch_adam_multi(int count, float* const* p, const float* const* g, float* const* m, float* const* v, const long long* n, float lr, float b1,
                                   float b2, float eps, int step, hipStream_t st) {
@@ -1490,13 +1522,13 @@ hipError_t cerb_launch_adam_multi(int count, float* const* p, const float* const
         if ((e = hipMemcpyAsync(dev_tab, host.data(), need, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;  // `host` may be rebuilt by the next call
     }
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
-    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)ch.size()), dim3(256), 0, st, (const AdamTensor*)dev_tab, (const int2*)((const char*)dev_tab + tb), lr, b1,
-                       b2, eps, bc1, bc2);
+    const AdamCoef k = adam_coef(b1, b2, step);
+    hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)ch.size()), dim3(256), 0, st, (const AdamTensor*)dev_tab, (const int2*)((const char*)dev_tab + tb), lr, eps,
+                       k.bc1, k.bc2, k.b1, k.b2, k.omb1, k.omb2);
     return hipGetLastError();
 }
 hipError_t cerb_launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, int step, hipStream_t st) {
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
-    hipLaunchKernelGGL(adam_kernel, dim3(gridfor(n)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, bc1, bc2);
+    const AdamCoef k = adam_coef(b1, b2, step);
+    hipLaunchKernelGGL(adam_kernel, dim3(gridfor(n)), dim3(256), 0, st, p, g, m, v, n, lr, eps, k.bc1, k.bc2, k.b1, k.b2, k.omb1, k.omb2);
     return hipGetLastError();
 }

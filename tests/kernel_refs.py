@@ -1,0 +1,170 @@
+"""Plain references of the training step's backward operations, one per kernel family of tests/test_kernel_parity_gpu.py (CPU, torch).
+
+Every operation is torch.nn.functional under autograd on the SAME inputs the kernel gets, in the dtype the caller names: float64 is the reference,
+float32 the yardstick `ref32` of the kernel's bar (err(kernel) <= k * err(ref32) + 1e-7 with err(a) = max|a - ref64| / max|ref64| per tensor).
+Activations are NHWC with a leading group axis [G][N][H][W][C], weights [G][Cout][Cin][k][k] -- the kernels' own layouts (tests/dev_kernels.py).
+Two references are written by hand: wgrad_wino_formula (the F(4x4,3x3) Winograd-domain weight gradient, the second yardstick of that kernel) and
+dilate2; tests/test_kernel_refs.py ties both to autograd on the host."""
+import torch
+import torch.nn.functional as F
+
+
+def err(a, ref64):
+    """max|a - ref64| / max|ref64| of one tensor; NaN / inf anywhere in `a` gives inf (a poisoned output that was accumulated into)."""
+    a = a.detach().to(torch.float64).cpu()
+    ref64 = ref64.detach().to(torch.float64)
+    assert a.shape == ref64.shape, (tuple(a.shape), tuple(ref64.shape))
+    if a.numel() == 0:
+        return 0.0
+    if not bool(torch.isfinite(a).all()):
+        return float("inf")
+    scale = float(ref64.abs().max())
+    d = float((a - ref64).abs().max())
+    return d / scale if scale > 0 else (0.0 if d == 0 else float("inf"))
+
+
+# ---- convolutions -------------------------------------------------------------------------------------------------------------------------------
+def conv_grads(x, dy, w, ks, stride, dt, bias_grad=True):
+    """x [G][N][H][W][Cin], dy [G][N][Ho][Wo][Cout], w [G][Cout][Cin][ks][ks] or None (zeros: the weight gradient of a convolution does not depend on the
+    weights) -> dw [G][Cout][Cin][ks][ks], db [G][Cout], dx [G][N][H][W][Cin] (dx only when w is given).  Padding ks // 2: a 3x3 stride-2 window reads rows
+    2 yo - 1 + ky."""
+    G, Cin, Cout = x.shape[0], x.shape[-1], dy.shape[-1]
+    dws, dbs, dxs = [], [], []
+    for g in range(G):
+        xg = x[g].permute(0, 3, 1, 2).to(dt).contiguous().requires_grad_(w is not None)
+        wg = (torch.zeros(Cout, Cin, ks, ks, dtype=dt) if w is None else w[g].to(dt).clone()).requires_grad_(True)
+        bg = torch.zeros(Cout, dtype=dt, requires_grad=True)
+        y = F.conv2d(xg, wg, bg, stride=stride, padding=ks // 2)
+        go = dy[g].permute(0, 3, 1, 2).to(dt)
+        assert y.shape == go.shape, (tuple(y.shape), tuple(go.shape))
+        y.backward(go)
+        dws.append(wg.grad)
+        dbs.append(bg.grad)
+        if w is not None:
+            dxs.append(xg.grad.permute(0, 2, 3, 1).contiguous())
+    return torch.stack(dws), torch.stack(dbs), (torch.stack(dxs) if dxs else None)
+
+
+_BT = [[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0], [0, 4, 0, -5, 0, 1]]
+_G = [[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]]
+_AT = [[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]]
+
+
+def wgrad_wino_formula(x, dy, dt):
+    """The algorithm of conv_wgrad_wino.hip evaluated plainly in `dt`, with the standard F(4x4,3x3) matrices (Y = A^T [(G g G^T) .* (B^T d B)] A):
+    dU = sum over the 4x4-output tiles of (A dY A^T) .* (B^T d B), dg = G^T dU G.  x [G][N][H][W][Cin], dy [G][N][H][W][Cout], H and W multiples of 4."""
+    BT, Gm, AT = torch.tensor(_BT, dtype=dt), torch.tensor(_G, dtype=torch.float64).to(dt), torch.tensor(_AT, dtype=dt)
+    out = []
+    for g in range(x.shape[0]):
+        xg, yg = x[g].permute(0, 3, 1, 2).to(dt), dy[g].permute(0, 3, 1, 2).to(dt)
+        N, Ci, H, W = xg.shape
+        Co, T = yg.shape[1], (H // 4) * (W // 4)
+        d = F.unfold(F.pad(xg, (1, 1, 1, 1)), 6, stride=4).view(N, Ci, 6, 6, T)   # the 6x6 input patch of every tile, zero padded
+        q = F.unfold(yg, 4, stride=4).view(N, Co, 4, 4, T)                        # its 4x4 output gradients
+        V = torch.einsum("ij,ncjkt,lk->ncilt", BT, d, BT)
+        Z = torch.einsum("ji,ncjkt,kl->ncilt", AT, q, AT)
+        dU = torch.einsum("noabt,niabt->oiab", Z, V)
+        out.append(torch.einsum("ax,oiab,by->oixy", Gm, dU, Gm))
+    return torch.stack(out)
+
+
+def stem_wgrad(tiles, dy, dt):
+    """tiles uint8 [N][H][W][3], dy [N][H][W][64] -> dw [64][3][7][7] of conv2d(tiles / 255, w, padding=3)."""
+    x = (tiles.permute(0, 3, 1, 2).to(dt) / 255).contiguous()
+    w = torch.zeros(64, 3, 7, 7, dtype=dt, requires_grad=True)
+    F.conv2d(x, w, padding=3).backward(dy.permute(0, 3, 1, 2).to(dt))
+    return w.grad
+
+
+# ---- BatchNorm ----------------------------------------------------------------------------------------------------------------------------------
+def bn_stats(y, dt, eps=1e-5):
+    """y [G][rows][C] -> mean, 1 / sqrt(biased var + eps), unbiased var, each [G][C]."""
+    v = y.to(dt)
+    m = v.mean(1)
+    var = v.var(1, unbiased=False)
+    n = v.shape[1]
+    return m, 1.0 / torch.sqrt(var + eps), var * (n / max(n - 1, 1))
+
+
+def bn_forward(y, gamma, beta, resid, relu, eval_groups, run_mean, run_var, dt, eps=1e-5):
+    """z = relu?(batch_norm(y) (+ resid)), per group; groups in eval_groups normalise with the running statistics.  Leaves (y, gamma, beta, resid) come
+    back too, for bn_backward."""
+    G = y.shape[0]
+    leaves, zs = [], []
+    for g in range(G):
+        yv = y[g].to(dt).clone().requires_grad_(True)
+        ga, be = gamma[g].to(dt).clone().requires_grad_(True), beta[g].to(dt).clone().requires_grad_(True)
+        rs = None if resid is None else resid[g].to(dt).clone().requires_grad_(True)
+        ev = g in eval_groups
+        z = F.batch_norm(yv, run_mean[g].to(dt).clone() if ev else None, run_var[g].to(dt).clone() if ev else None, ga, be, training=not ev, eps=eps)
+        if rs is not None:
+            z = z + rs
+        if relu:
+            z = F.relu(z)
+        leaves.append((yv, ga, be, rs))
+        zs.append(z)
+    return leaves, zs
+
+
+def bn_backward(leaves, zs, dz, dt):
+    """-> dy [G][rows][C], dresid (or None), dgamma [G][C], dbeta [G][C]"""
+    for g, z in enumerate(zs):
+        z.backward(dz[g].to(dt))
+    dy = torch.stack([l[0].grad for l in leaves])
+    dres = None if leaves[0][3] is None else torch.stack([l[3].grad for l in leaves])
+    return dy, dres, torch.stack([l[1].grad for l in leaves]), torch.stack([l[2].grad for l in leaves])
+
+
+# ---- decoder entry: out_g = skip + up2(prev_g) ---------------------------------------------------------------------------------------------------
+def upadd_grads(dout, shared_prev, live, dt):
+    """dout [G][N][H][W][C]; live: per group, False = the group's gradient counts as zero.  -> dskip [N][H][W][C], dprev [G or 1][N][H/2][W/2][C]
+    (shared_prev: one `prev` feeds every group, its gradient is the sum over the groups)."""
+    G, N, H, W, C = dout.shape
+    skip = torch.zeros(N, C, H, W, dtype=dt, requires_grad=True)
+    prev = torch.zeros(1 if shared_prev else G, N, C, H // 2, W // 2, dtype=dt, requires_grad=True)
+    for g in range(G):
+        out = skip + F.interpolate(prev[0 if shared_prev else g], scale_factor=2, mode="bilinear", align_corners=False)
+        out.backward(dout[g].permute(0, 3, 1, 2).to(dt) * (1.0 if live[g] else 0.0))
+    return skip.grad.permute(0, 2, 3, 1).contiguous(), prev.grad.permute(0, 1, 3, 4, 2).contiguous()
+
+
+# ---- max-pool 3x3 / 2 / 1 -----------------------------------------------------------------------------------------------------------------------
+def maxpool(x, dy, dt):
+    """x [N][H][W][C], dy [N][H/2][W/2][C] -> pooled map, dx (the gradient goes to the element torch's CPU backward picks: the first maximum in scan order)."""
+    xv = x.permute(0, 3, 1, 2).to(dt).contiguous().requires_grad_(True)
+    p = F.max_pool2d(xv, 3, 2, 1)
+    p.backward(dy.permute(0, 3, 1, 2).to(dt).contiguous())
+    return p.detach().permute(0, 2, 3, 1).contiguous(), xv.grad.permute(0, 2, 3, 1).contiguous()
+
+
+# ---- pointwise layers ---------------------------------------------------------------------------------------------------------------------------
+def pointwise_grads(x, dy, w, in_scale, dt):
+    """out = (x * in_scale) @ w^T + b on [rows][cin] -> dx, dw [cout][cin], db [cout]"""
+    xv = x.to(dt).clone().requires_grad_(True)
+    wv = w.to(dt).clone().requires_grad_(True)
+    b = torch.zeros(w.shape[0], dtype=dt, requires_grad=True)
+    xs = xv if in_scale is None else xv * in_scale.to(dt)
+    (xs @ wv.t() + b).backward(dy.to(dt))
+    return xv.grad, wv.grad, b.grad
+
+
+# ---- small pieces -------------------------------------------------------------------------------------------------------------------------------
+def colsum(d, dt):
+    """d [G][rows][C] -> [G][C]"""
+    return d.to(dt).sum(1)
+
+
+def crop_gap(x, dg, y0, ch, x0, cw, dt):
+    """x [N][H][W][C] -> mean over the window [y0, y0 + ch) x [x0, x0 + cw): [N][C]; and the gradient of x for the upstream dg [N][C]"""
+    xv = x.to(dt).clone().requires_grad_(True)
+    out = xv[:, y0:y0 + ch, x0:x0 + cw, :].mean((1, 2))
+    out.backward(dg.to(dt))
+    return out.detach(), xv.grad
+
+
+def dilate2(dy):
+    """dy [n][H/2][W/2][C] -> D [n][H][W][C] with D[:, 2 y, 2 x] = dy[:, y, x], zero elsewhere (exact)"""
+    n, h, w, c = dy.shape
+    d = torch.zeros(n, 2 * h, 2 * w, c, dtype=dy.dtype)
+    d[:, ::2, ::2, :] = dy
+    return d

@@ -64,6 +64,46 @@ def test_host_codec_library_exports_what_its_header_declares():
     assert L.cerb_host_version() >= 1
 
 
+def _exported(path):
+    """names the shared library DEFINES in its dynamic symbol table (ELF64, little endian: .dynsym and the string table it links to)"""
+    import struct
+
+    b = open(path, "rb").read()
+    assert b[:6] == b"\x7fELF\x02\x01", path
+    shoff, = struct.unpack_from("<Q", b, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", b, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for sec in secs:
+        if sec[1] != 11:  # SHT_DYNSYM
+            continue
+        off, size, link, entsize = sec[4], sec[5], sec[6], sec[9]
+        stroff = secs[link][4]
+        for o in range(off, off + size, entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", b, o)
+            if st_shndx != 0:  # defined here
+                names.add(b[stroff + st_name:b.index(b"\0", stroff + st_name)].decode())
+    return names
+
+
+def test_product_library_exports_no_developer_entry():
+    """The test-only entry layer (cerberus_amd/csrc/dev_entry.hip: cerb_dev_* wrappers over single launchers, for tests/dev_kernels.py) is linked into the
+    developers' library only: libcerberus_hip.so exports none of it, and libcerberus_hip_dev.so exports every entry the bindings declare."""
+    import dev_kernels
+    from cerberus_amd import _lib, build
+
+    assert os.path.exists(_lib.LIB_PATH) and os.path.exists(build.LIB_DEV), "run `python -m cerberus_amd.build` first"
+    prod = _exported(build.LIB)
+    assert "cerb_net_forward" in prod and "cerb_adam_step" in prod  # (the parser sees the exports)
+    assert [n for n in prod if n.startswith("cerb_dev_")] == []
+    dev = _exported(build.LIB_DEV)
+    src = open(os.path.join(ROOT, "cerberus_amd", "csrc", "dev_entry.hip")).read()
+    declared = sorted(set(re.findall(r"\b(cerb_dev_[a-z0-9_]+)\s*\(", re.sub(r"//[^\n]*", "", src))))
+    assert declared == dev_kernels.ENTRIES and len(declared) >= 25
+    assert sorted(n for n in dev if n.startswith("cerb_dev_")) == declared
+    assert "dev_entry.hip" in build.DEV_ONLY_SOURCES and "dev_entry.hip" not in build.SOURCES
+
+
 def test_version_and_error_string():
     from cerberus_amd import _lib
 

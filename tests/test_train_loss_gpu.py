@@ -894,3 +894,190 @@ def test_batchnorm_backward_sums_from_the_data_gradient_equal_the_reduction_pass
             den = float(np.linalg.norm(a) * np.linalg.norm(b))
             assert den > 0 and float(a @ b) / den > 0.99999, k
             assert float(np.abs(a - b).max()) <= 2e-4 * float(np.abs(b).max()), (k, float(np.abs(a - b).max()), float(np.abs(b).max()))
+
+
+# =====================================================================================================================================================
+# Adam beyond the first step (at step 1 the update degenerates to lr * sign(g) for any beta and any bias correction): cerb_adam_step,
+# cerb_adam_step_multi and cerberus_amd.train.Adam against torch.optim.Adam on float64 CPU copies, after EVERY one of 12 steps.  The bar is the one of
+# tests/test_kernel_parity_gpu.py: err(kernel) <= K_ADAM * err(torch float32) + 1e-7 with err(a) = max|a - ref64| / max|ref64| per tensor, for the
+# parameter with its accumulated CHANGE as the scale (the parameter itself is O(1): its own size would hide the update).
+ADAM_CHUNK = 16384  # train_kernels.hip: a block of adam_multi_kernel takes one 16384-element chunk of one tensor
+ADAM_SIZES = (1, 63, ADAM_CHUNK - 1, ADAM_CHUNK, ADAM_CHUNK + 1, 2 * ADAM_CHUNK + 5, 0)
+ADAM_SIZES_B = (ADAM_CHUNK + 1, 1, 5, 2 * ADAM_CHUNK, 70, ADAM_CHUNK - 1, 3)  # same length, other tensors and sizes
+K_ADAM = 4
+_adam_cache = {}
+
+
+def _adam_problem(sizes, seed, steps):
+    """Start values and a FRESH gradient per step.  By element index i: i % 4 == 0 randn (signs change between steps), 1 exactly 0 on every step,
+    2 around 1e-12 (eps-dominated), 3 around 1e4."""
+    gen = torch.Generator().manual_seed(seed)
+    p0 = [torch.randn(n, generator=gen) for n in sizes]
+    grads = []
+    for _ in range(steps):
+        gs = []
+        for n in sizes:
+            g, k = torch.randn(n, generator=gen), torch.arange(n) % 4
+            gs.append(g * torch.tensor([1.0, 0.0, 1e-12, 1e4])[k])
+        grads.append(gs)
+    return p0, grads
+
+
+def _adam_torch(p0, grads, dt, step_lr):
+    """torch.optim.Adam (lr 1e-3, betas (0.9, 0.999), eps 1e-8) in dtype dt; step_lr: StepLR(8, 0.1) drops the rate to 1e-4 after step 8.
+    -> per step, per tensor (param, exp_avg, exp_avg_sq)"""
+    ps = [p.to(dt).clone().requires_grad_(True) for p in p0]
+    opt = torch.optim.Adam(ps, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, foreach=False)
+    sched = torch.optim.lr_scheduler.StepLR(opt, 8, 0.1) if step_lr else None
+    out = []
+    for gs in grads:
+        for p, g in zip(ps, gs):
+            p.grad = g.to(dt).clone()
+        opt.step()
+        if sched:
+            sched.step()
+        out.append([(p.detach().clone(), opt.state[p]["exp_avg"].clone(), opt.state[p]["exp_avg_sq"].clone()) for p in ps])
+    return out
+
+
+def _adam_case(sizes, seed, steps, step_lr):
+    """the problem and its two torch runs, computed once and shared (never modified)"""
+    key = (sizes, seed, steps, step_lr)
+    if key not in _adam_cache:
+        p0, grads = _adam_problem(sizes, seed, steps)
+        _adam_cache[key] = (p0, grads, _adam_torch(p0, grads, torch.float64, step_lr), _adam_torch(p0, grads, torch.float32, step_lr))
+    return _adam_cache[key]
+
+
+def _adam_compare(tag, p0, got, ref64, ref32, bad):
+    """got / ref64 / ref32: per tensor (param, exp_avg, exp_avg_sq) after the same step"""
+    import kernel_refs as R
+
+    worst = 0.0
+    for i, (g3, r3, y3) in enumerate(zip(got, ref64, ref32)):
+        start = p0[i].to(torch.float64)
+        for name, g, r, y in zip(("param", "exp_avg", "exp_avg_sq"), g3, r3, y3):
+            g, y = g.detach().cpu().to(torch.float64), y.to(torch.float64)
+            if name == "param":  # the accumulated change is the scale
+                g, r, y = g - start, r - start, y - start
+            eg, ey = R.err(g, r), R.err(y, r)
+            if eg > 1e-7:
+                worst = max(worst, eg / ey if ey > 0 else float("inf"))
+            if not eg <= K_ADAM * ey + 1e-7:
+                bad.append("%s tensor %d (%d elements) %s: err %.3e > %d * %.3e + 1e-7" % (tag, i, p0[i].numel(), name, eg, K_ADAM, ey))
+        # an element whose gradient is exactly 0 on every step never moves: parameter and both moments bit-identical to their start
+        z = torch.arange(p0[i].numel()) % 4 == 1
+        if not (torch.equal(g3[0].cpu()[z], p0[i][z]) and not bool(g3[1].cpu()[z].any()) and not bool(g3[2].cpu()[z].any())):
+            bad.append("%s tensor %d: an element with zero gradient moved" % (tag, i))
+    return worst
+
+
+def _adam_multi(L, ps, gs, ms, vs, lr, step):
+    import ctypes as C
+
+    n = len(ps)
+    arr = [(C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in ts]) for ts in (ps, gs, ms, vs)]
+    nn = (C.c_longlong * n)(*[p.numel() for p in ps])
+    return L.cerb_adam_step_multi(n, arr[0], arr[1], arr[2], arr[3], nn, lr, 0.9, 0.999, 1e-8, step, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+
+def test_adam_twelve_steps_with_a_rate_drop_vs_torch_float64():
+    """cerberus_amd.train.Adam + StepLR: bias corrections, moment recurrences, where eps is added and a learning rate that changes mid-run, at tensor
+    sizes around the 16384-element chunk of the multi-tensor kernel (and one empty tensor)."""
+    from cerberus_amd.train import Adam, StepLR
+
+    p0, grads, ref64, ref32 = _adam_case(ADAM_SIZES, 31, 12, True)
+    params = {"t%d" % i: p.clone().cuda() for i, p in enumerate(p0)}
+    opt = Adam(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+    sched = StepLR(opt, 8)
+    bad, worst = [], 0.0
+    for s, gs in enumerate(grads):
+        assert abs(opt.lr - (1e-3 if s < 8 else 1e-4)) < 1e-12
+        opt.step(params, {"t%d" % i: g.cuda() for i, g in enumerate(gs)})
+        sched.step()
+        torch.cuda.synchronize()
+        got = [(params["t%d" % i],) + tuple(opt.state["t%d" % i]) for i in range(len(p0))]
+        w = _adam_compare("step %d" % (s + 1), p0, got, ref64[s], ref32[s], bad)
+        worst = max(worst, w)
+        print("adam step %d: worst err / yardstick ratio %.2f" % (s + 1, w))
+    print("adam: worst err / yardstick ratio %.2f (K = %d)" % (worst, K_ADAM))
+    assert not bad, bad[:12]
+
+
+def test_adam_chunk_table_follows_the_tensor_list():
+    """cerb_launch_adam_multi keeps its chunk table on the device and uploads it only when it differs from the last call's: list A, then a list B of the
+    same length but other tensors and sizes, then A again on one stream -- and two Adam objects alternating -- must each update their own tensors."""
+    from cerberus_amd import _lib
+    from cerberus_amd.train import Adam
+
+    L = _lib.lib()
+    a0, ag, a64, a32 = _adam_case(ADAM_SIZES, 31, 12, True)   # (the first steps do not depend on the schedule)
+    b0, bg, b64, b32 = _adam_case(ADAM_SIZES_B, 32, 2, False)
+    bad = []
+    dev = {}
+    for tag, p0 in (("A", a0), ("B", b0)):
+        dev[tag] = ([p.clone().cuda() for p in p0], [torch.zeros_like(p).cuda() for p in p0], [torch.zeros_like(p).cuda() for p in p0])
+    for tag, step, grads, p0, r64, r32 in (("A", 1, ag, a0, a64, a32), ("B", 1, bg, b0, b64, b32), ("A", 2, ag, a0, a64, a32), ("B", 2, bg, b0, b64, b32)):
+        ps, ms, vs = dev[tag]
+        gs = [g.cuda() for g in grads[step - 1]]
+        assert _adam_multi(L, ps, gs, ms, vs, 1e-3, step) == 0, L.cerb_last_error()
+        torch.cuda.synchronize()
+        _adam_compare("list %s step %d" % (tag, step), p0, list(zip(ps, ms, vs)), r64[step - 1], r32[step - 1], bad)
+    # two optimisers alternating on one stream share the table and re-upload it every step
+    opts = {"A": Adam(), "B": Adam()}
+    prm = {"A": {"t%d" % i: p.clone().cuda() for i, p in enumerate(a0)}, "B": {"t%d" % i: p.clone().cuda() for i, p in enumerate(b0)}}
+    for step in (1, 2):
+        for tag, grads, p0, r64, r32 in (("A", ag, a0, a64, a32), ("B", bg, b0, b64, b32)):
+            opts[tag].step(prm[tag], {"t%d" % i: g.cuda() for i, g in enumerate(grads[step - 1])})
+            torch.cuda.synchronize()
+            got = [(prm[tag]["t%d" % i],) + tuple(opts[tag].state["t%d" % i]) for i in range(len(p0))]
+            _adam_compare("Adam object %s step %d" % (tag, step), p0, got, r64[step - 1], r32[step - 1], bad)
+    assert not bad, bad[:12]
+
+
+def test_adam_single_tensor_entry_equals_the_multi_tensor_one_bit_for_bit():
+    import ctypes as C
+
+    from cerberus_amd import _lib
+
+    L = _lib.lib()
+    p0, grads, ref64, ref32 = _adam_case(ADAM_SIZES, 31, 12, True)
+    i = ADAM_SIZES.index(ADAM_CHUNK + 1)
+    one = [p0[i].clone().cuda(), torch.zeros(ADAM_CHUNK + 1, device="cuda"), torch.zeros(ADAM_CHUNK + 1, device="cuda")]
+    many = [t.clone() for t in one]
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    bad = []
+    for s in range(12):
+        lr, g = (1e-3 if s < 8 else 1e-4), grads[s][i].cuda()
+        assert L.cerb_adam_step(one[0].data_ptr(), g.data_ptr(), one[1].data_ptr(), one[2].data_ptr(), g.numel(), lr, 0.9, 0.999, 1e-8, s + 1, st) == 0, L.cerb_last_error()
+        assert _adam_multi(L, [many[0]], [g], [many[1]], [many[2]], lr, s + 1) == 0, L.cerb_last_error()
+        torch.cuda.synchronize()
+        for name, a, b in zip(("param", "exp_avg", "exp_avg_sq"), one, many):
+            assert torch.equal(a, b), "step %d: %s of cerb_adam_step differs from cerb_adam_step_multi" % (s + 1, name)
+        _adam_compare("cerb_adam_step step %d" % (s + 1), [p0[i]], [tuple(one)], [ref64[s][i]], [ref32[s][i]], bad)
+    assert not bad, bad[:12]
+
+
+def test_adam_entries_refuse_bad_arguments():
+    """step counts from 1 and every tensor of a list needs its four pointers: the documented error (return code 1 and a message), not a launch"""
+    import ctypes as C
+
+    from cerberus_amd import _lib
+
+    L = _lib.lib()
+    t = [torch.ones(8, device="cuda") for _ in range(4)]
+    keep = [x.clone() for x in t]
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert L.cerb_adam_step(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(), 8, 1e-3, 0.9, 0.999, 1e-8, 0, st) == 1
+    assert b"cerb_adam_step" in L.cerb_last_error()
+    assert L.cerb_adam_step(t[0].data_ptr(), None, t[2].data_ptr(), t[3].data_ptr(), 8, 1e-3, 0.9, 0.999, 1e-8, 1, st) == 1
+    assert _adam_multi(L, [t[0]], [t[1]], [t[2]], [t[3]], 1e-3, 0) == 1
+    assert b"cerb_adam_step_multi" in L.cerb_last_error()
+    for hole in range(4):  # a null pointer in one of the four lists, second tensor of two
+        arr = [(C.c_void_p * 2)(t[k].data_ptr(), None if k == hole else t[k].data_ptr()) for k in range(4)]
+        nn = (C.c_longlong * 2)(4, 4)
+        assert L.cerb_adam_step_multi(2, arr[0], arr[1], arr[2], arr[3], nn, 1e-3, 0.9, 0.999, 1e-8, 1, st) == 1
+        assert b"null tensor" in L.cerb_last_error()
+    torch.cuda.synchronize()
+    for a, b in zip(t, keep):
+        assert torch.equal(a, b), "a refused call changed a tensor"
