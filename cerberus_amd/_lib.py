@@ -14,6 +14,7 @@ EXPORTS = [
     "cerb_target_workspace_bytes", "cerb_target_window_workspace_bytes", "cerb_target_element", "cerb_target_pixel_maps", "cerb_target_eroded_maps",
     "cerb_target_weight_maps",
     "cerb_valid_stats_bytes", "cerb_valid_stats_reset", "cerb_valid_stats_accumulate",
+    "cerb_jpeg_workspace_bytes", "cerb_jpeg_decode_stream", "cerb_jpeg_read_tiles", "cerb_jpeg_decode_window",
 ]
 
 
@@ -175,6 +176,13 @@ def lib():
     L.cerb_valid_stats_bytes.restype = C.c_size_t
     L.cerb_valid_stats_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.cerb_valid_stats_accumulate.argtypes = [C.POINTER(ValidHeads), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_jpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.cerb_jpeg_workspace_bytes.restype = C.c_size_t
+    L.cerb_jpeg_decode_stream.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.cerb_jpeg_read_tiles.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    L.cerb_jpeg_decode_window.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

@@ -42,6 +42,9 @@ WSI_OPTIONS = _COMMON + [
     ("--reference_tiling", False, False, "(not in the reference) nuclei instances through the reference's own 4096 x 4096 tiles, 64-px margins, strips and "
                                          "cross sections (infer/wsi.py:81-268, 642-684; cerberus_amd/ref_tiling.py) instead of exact band ownership: the "
                                          "reference's instance set, including the few seam instances its scheme drops; tiles are sharded over the ranks"),
+    ("--jpeg_decode", True, "host", "(not in the reference) host | device: where the JPEG tiles of .svs / tiled TIFF slides are decoded -- host: PIL / libjpeg, tile by "
+                                    "tile (unless CERB_JPEG_DECODE says otherwise); device: native Huffman pass on the host, inverse DCT / up-sampling / colour in HIP "
+                                    "kernels, the same bytes (sets CERB_JPEG_DECODE=device; cerberus_amd/jpeg_device.py)"),
 ]
 
 

@@ -86,7 +86,14 @@ def plan_slide(net, slide_hw, win, out, batch, rank=0, world=1, want_twin=True, 
     fwd = forward_workspace_bytes(batch, win)
     budget = hbm_budget() if budget is None else int(budget)
     y0, y1 = geo.input_rows(r0, r1)
-    slab = (y1 - y0) * geo.W * 3
+    # CERB_JPEG_DECODE=device: the uploader's ring holds coefficient buffers on the device beside the slab (cerberus_amd/jpeg_device.py; an estimate
+    # at the processing resolution's width -- the switch only takes effect on slides with JPEG tiles)
+    jpeg_ring = 0
+    if os.environ.get("CERB_JPEG_DECODE") == "device":
+        from .jpeg_device import ring_bytes_estimate
+
+        jpeg_ring = ring_bytes_estimate(geo.W)
+    slab = (y1 - y0) * geo.W * 3 + jpeg_ring
     halo = (2 * margin * cw) if world > 1 else 0
     call_px = min(px, int(max_band_px) if max_band_px else px) + 2 * margin * cw
     phase_infer = slab
@@ -109,7 +116,7 @@ def plan_slide(net, slide_hw, win, out, batch, rank=0, world=1, want_twin=True, 
         if rs < min_rows:
             break
         sub_px = rs * geo.out * cw
-        sub_slab = (rs * geo.out + 2 * geo.ctx + 2) * geo.W * 3
+        sub_slab = (rs * geo.out + 2 * geo.ctx + 2) * geo.W * 3 + jpeg_ring
         strips = 2 * 3 * margin * cw * 8 + halo * (cb_inst + 4)
         need = sub_slab + 2 * sub_px * cb_all + tail + px * ((cb_all - cb_inst) + LABEL_BYTES_PX) + LABEL_WS_BYTES_PX * (sub_px + 2 * margin * cw) + 2 * sub_px * 4 + strips + fwd + RESERVE_BYTES
         best = need if best is None else min(best, need)

@@ -620,17 +620,36 @@ class SlabUploader(object):
         # tile row a chunk boundary cuts is decoded by both neighbours).  CERB_DEVICE_RESAMPLE=0: the host path.
         self.plan = host.device_plan() if (hasattr(host, "device_plan") and os.environ.get("CERB_DEVICE_RESAMPLE", "1") != "0") else None
         self.stage, self.tabs, self.col_tabs = None, [None] * nb, None
+        # CERB_JPEG_DECODE=device (opt-in): the JPEG tiles of a TIFF / .svs level leave the host as quantised coefficients -- Huffman pass in one native
+        # call per chunk, inverse DCT / up-sampling / colour on the device (cerberus_amd/jpeg_device.py) -- straight into the slab rows, or into the
+        # staging buffer the reduction kernels read.  The ring then holds coefficient buffers (pinned + device) instead of pinned pixels.
+        self.jpeg, self.jbuf = None, None
+        if os.environ.get("CERB_JPEG_DECODE") == "device":
+            from . import jpeg_device
+
+            self.jpeg = jpeg_device.uploader_source(host, self.plan)
         if self.plan is not None:
             pl = self.plan
             src_row = pl.lw * 3
             self.src_tiles = max(2 if pl.k is not None else 4, (4 * int(chunk_bytes)) // max(1, src_row * pl.tile_rows))
             cap = min((self.src_tiles + 1) * pl.tile_rows + int(np.ceil(pl.rel)) + 2, pl.lh)
-            self.pinned = [_take_pinned((cap, pl.lw, 3)) for _ in range(nb)]
+            if self.jpeg is None:
+                self.pinned = [_take_pinned((cap, pl.lw, 3)) for _ in range(nb)]
             self.stage = [torch.empty((cap, pl.lw, 3), dtype=torch.uint8, device=self.dev) for _ in range(nb)]
             if pl.k is None:
                 self.col_tabs = [torch.from_numpy(np.ascontiguousarray(t)).to(self.dev) for t in pl.col_tables()]
         else:
-            self.pinned = [_take_pinned((min(self.chunk, max(1, self.rows)), self.w, 3)) for _ in range(nb)]
+            cap = min(self.chunk, max(1, self.rows))
+            if self.jpeg is None:
+                self.pinned = [_take_pinned((cap, self.w, 3)) for _ in range(nb)]
+        if self.jpeg is not None:
+            from . import jpeg_device
+
+            p = self.jpeg[0].levels[self.jpeg[1]]
+            n_tiles = jpeg_device.max_window_tiles(p, cap)
+            self.pinned = [_take_pinned((jpeg_device.workspace_bytes(n_tiles, p.tw, p.th)[0],)) for _ in range(nb)]
+            self.jbuf = [jpeg_device.Buffers(n_tiles, p.tw, p.th, self.dev, pinned=self.pinned[0])]
+            self.jbuf += [jpeg_device.Buffers(n_tiles, p.tw, p.th, self.dev, pinned=t, scratch=self.jbuf[0].scratch) for t in self.pinned[1:]]
         self.busy = [None] * nb  # event after which a staging buffer may be overwritten
         self.copy_stream = torch.cuda.Stream(device=self.dev)
         self.next_row, self.k, self.last_event = 0, 0, None
@@ -652,10 +671,14 @@ class SlabUploader(object):
         else:
             n = min((a // self.chunk + 1) * self.chunk - a, self.rows - self.next_row)
             t0 = time.perf_counter()
-            np.copyto(self.pinned[i][:n].numpy(), self.host[self.y0 + self.next_row: self.y0 + self.next_row + n])
+            if self.jpeg is not None:
+                self._jpeg_window(i, a, a + n, self.slab[self.next_row: self.next_row + n])
+            else:
+                np.copyto(self.pinned[i][:n].numpy(), self.host[self.y0 + self.next_row: self.y0 + self.next_row + n])
             self.read_s += time.perf_counter() - t0
             with torch.cuda.stream(self.copy_stream):
-                self.slab[self.next_row: self.next_row + n].copy_(self.pinned[i][:n], non_blocking=True)
+                if self.jpeg is None:
+                    self.slab[self.next_row: self.next_row + n].copy_(self.pinned[i][:n], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.copy_stream)
         with self._cv:
@@ -663,6 +686,17 @@ class SlabUploader(object):
             self.next_row += n
             self.k += 1
             self._cv.notify_all()
+
+    def _jpeg_window(self, i, sy0, sy1, dst):
+        """rows [sy0, sy1) of the JPEG level, full width, into dst (device rows) through ring slot i on the copy stream; tiles the native decoder does
+        not take go through the reader's own decode and are copied into place on the same stream"""
+        from . import jpeg_device
+
+        r, lvl = self.jpeg
+        w = r.levels[lvl].w
+        back = jpeg_device.decode_window(r, lvl, 0, sy0, w, sy1, dst, self.copy_stream, self.jbuf[i])
+        if back:
+            jpeg_device.place_fallback(r, lvl, (0, sy0, w, sy1), back, dst, self.copy_stream)
 
     def _issue_resampled(self, i, a):
         """output rows [a, a + n) of the slide from the stored level's rows: decode -> pinned -> device staging -> reduction into the slab"""
@@ -674,14 +708,18 @@ class SlabUploader(object):
         n = min(b - a, self.rows - self.next_row)
         sy0, sy1 = pl.source_rows(a, a + n)
         m = sy1 - sy0
-        assert 0 < m <= self.pinned[i].shape[0], (m, self.pinned[i].shape, a, n)
+        assert 0 < m <= self.stage[i].shape[0], (m, self.stage[i].shape, a, n)
         t0 = time.perf_counter()
-        pl.read(sy0, sy1, out=self.pinned[i].numpy())
+        if self.jpeg is not None:
+            self._jpeg_window(i, sy0, sy1, self.stage[i][:m])
+        else:
+            pl.read(sy0, sy1, out=self.pinned[i].numpy())
         self.read_s += time.perf_counter() - t0
         L = _lib.lib()
         dst = self.slab[self.next_row: self.next_row + n]
         with torch.cuda.stream(self.copy_stream):
-            self.stage[i][:m].copy_(self.pinned[i][:m], non_blocking=True)
+            if self.jpeg is None:
+                self.stage[i][:m].copy_(self.pinned[i][:m], non_blocking=True)
             st = C.c_void_p(self.copy_stream.cuda_stream)
             if pl.k is not None:
                 _lib.check(L.cerb_resample_box(self.stage[i].data_ptr(), pl.lw * 3, m, pl.lw, pl.k, dst.data_ptr(), self.w * 3, n, self.w, st))

@@ -432,6 +432,50 @@ size_t cerb_valid_stats_bytes(int n_heads);
 int cerb_valid_stats_reset(int64_t* acc, int n_heads, void* hip_stream);
 int cerb_valid_stats_accumulate(const cerb_valid_heads* heads, const uint8_t* flags, int n, int h, int w, int64_t* acc, void* hip_stream);
 
+/* ---- JPEG tiles of a TIFF / .svs level: host Huffman pass, device IDCT / up-sampling / colour (cerberus_amd/jpeg_device.py) -------------------
+ * Replaces, for compression-7 tiles, the per-tile PIL decode of the slide reader (cerberus_amd/reader.py: TiffReader._decode; the reference reads
+ * slides through tiatoolbox's WSIReader on 12 DataLoader workers, infer/wsi.py:936-950) and returns ITS bytes.  The only serial part of a baseline JPEG
+ * decode is the entropy decoder (csrc/jpeg_entropy.h, which states what is accepted, "unsupported" and "corrupt"); it runs on host threads and hands
+ * QUANTISED coefficients over, everything after it runs in two kernels (csrc/jpeg_kernels.hip).
+ *
+ * Buffer layout ("stream buffer", the same bytes on the host and on the device): n_tiles tile headers (cerb_jpeg_hdr of jpeg_entropy.h, 464 bytes each:
+ * status, size, sampling, colour decision, MCU grid, position in the level, coefficient offset, three de-zigzagged uint16 quantisation tables),
+ * padded to a multiple of 256 bytes, then the int16 coefficients of the tiles that decoded, in natural order: per tile, per component, a raster of
+ * (mcu_rows v) x (mcu_cols h) blocks of 64.
+ *   cerb_jpeg_workspace_bytes(n_tiles, tile_w, tile_h, which): which = 0 the stream buffer for n_tiles tiles of that size whatever their sampling
+ *                           (pinned host memory and its device copy); which = 1 the device scratch of cerb_jpeg_decode_window (the component planes).
+ *   cerb_jpeg_decode_stream one stream (+ optional JPEGTables stream) -> header + coefficients; RETURNS THE STATUS: 0 decoded, 1 unsupported (not an
+ *                           error), -1 corrupt, -2 the coefficients exceed coef_cap (int16 units).  No device involved.
+ *   cerb_jpeg_read_tiles    HOST half of a window: pread of n_tiles byte ranges (offsets / counts) of fd and their entropy decode on up to n_threads
+ *                           (<= 64) threads that take tiles off a shared counter, like cerb_host_tiff_read_tiles; the interpreter is not involved.  gx0 /
+ *                           gy0: every tile's position in its level.  tables / n_tables: the page's JPEGTables (tag 347) or none.  photometric_rgb: the page's
+ *                           PhotometricInterpretation is 2 (the components are R, G, B whatever the stream's markers say).  buf: 16-byte aligned, at least
+ *                           cerb_jpeg_workspace_bytes(.., 0) bytes.  *used_bytes: the prefix of buf to copy to the device.  unsupported[0 .. *n_unsupported):
+ *                           ascending indices of the tiles the caller must decode another way (also every stream whose size is not tile_w x tile_h); their
+ *                           headers say so and the device half skips them.  A corrupt tile or a short read fails the call (1, cerb_last_error) with
+ *                           *bad_tile = the first such index, else -1.
+ *   cerb_jpeg_decode_window DEVICE half, two launches per 65535 tiles on hip_stream, no allocation, no synchronisation: dev_buf = the device copy of
+ *                           the stream buffer's first dev_bytes bytes; scratch: 8-byte aligned, cerb_jpeg_workspace_bytes(.., 1) bytes; the part of every
+ *                           decoded tile inside the window [x0, x1) x [y0, y1) of the level goes to dst + (y - y0) dst_row_stride + (x - x0) 3 (uint8 RGB).
+ *                           Offsets in the headers are checked against dev_bytes / scratch_bytes; nothing outside the window is written.
+ * Arithmetic (all integers, >> arithmetic, products in 64 bits), equal to PIL 12 / libjpeg-turbo bit for bit on what encoders write:
+ *   dequantise c[k] q[k]; inverse DCT "islow" with 13-bit constants (2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172), pass 1 down
+ *   the columns rounded to (x + 1024) >> 11, pass 2 along the rows (x + 131072) >> 18, sample = clamp(x + 128, 0, 255);
+ *   chroma planes are cut to ceil(W / 2) (x ceil(H / 2)) BEFORE up-sampling.  4:2:2, per row: out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] =
+ *   (3 in[i] + in[i+1] + 2) >> 2, the first and the last output copy their input.  4:2:0: s[i] = 3 in[r][i] + in[r'][i] with r' the nearer neighbour row
+ *   (clamped), out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4 with i +- 1 clamped; then cropped to W x H;
+ *   YCbCr -> RGB (cb, cr less 128): R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768)
+ *   >> 16), clamped.  Outside the claim: libjpeg's range-limit table WRAPS samples more than about 384 beyond 0 .. 255 where this clamps, and its SIMD
+ *   inverse DCT keeps 16-bit intermediates; only hostile streams (no encoder's output) get there. */
+size_t cerb_jpeg_workspace_bytes(int n_tiles, int tile_w, int tile_h, int which);
+int cerb_jpeg_decode_stream(const uint8_t* tables, long long n_tables, const uint8_t* src, long long n_src, int photometric_rgb, void* hdr,
+                            int16_t* coefs, long long coef_cap, long long* coef_used);
+int cerb_jpeg_read_tiles(int fd, int n_tiles, const int64_t* offsets, const int64_t* counts, const int32_t* gx0, const int32_t* gy0, int tile_w,
+                         int tile_h, const uint8_t* tables, long long n_tables, int photometric_rgb, void* buf, size_t buf_bytes, int n_threads,
+                         size_t* used_bytes, int32_t* bad_tile, int32_t* n_unsupported, int32_t* unsupported);
+int cerb_jpeg_decode_window(const void* dev_buf, size_t dev_bytes, int n_tiles, int tile_w, int tile_h, uint8_t* scratch, size_t scratch_bytes,
+                            uint8_t* dst, long long dst_row_stride, int x0, int y0, int x1, int y1, void* hip_stream);
+
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
 int cerb_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* synchronises on ev_stop */

@@ -86,6 +86,10 @@ def _open_slide(path, proc_mpp):
 def main(argv=None):
     args = parse("run_infer_wsi.py", WSI_OPTIONS, argv, version="CoBi Gland Inference")
     require_model(args)
+    if args["--jpeg_decode"] not in ("host", "device"):
+        sys.exit("--jpeg_decode takes host or device, got %r" % args["--jpeg_decode"])
+    if args["--jpeg_decode"] == "device":  # (before the ranks are started: they inherit it)
+        os.environ["CERB_JPEG_DECODE"] = "device"
     from cerberus_amd import launch
 
     backend = os.environ.get("CERB_DIST_BACKEND", "nccl")
