@@ -54,7 +54,7 @@ extern "C" int cerb_net_create(const char* const* decoder_names, const char* con
             if (d.head == "INST") d.kind = 0;
             else if (d.head == "TYPE") d.kind = 1;
             else { delete net; return fail("decoder " + d.name + ": head must be INST or TYPE, got " + d.head); }
-            if (d.kind == 0 && d.out_ch != 3) { delete net; return fail("INST heads must have 3 channels (infer_step keeps channels 1..2)"); }
+            if (d.kind == 0 && d.out_ch != 2 && d.out_ch != 3) { delete net; return fail("INST heads must have 2 or 3 channels (infer_step keeps channels 1..out_ch-1), got " + std::to_string(d.out_ch)); }
             if (d.out_ch < 2 || d.out_ch > 8) { delete net; return fail("head out_ch must be 2..8"); }
             int trunk = -1;
             for (size_t t = 0; t < net->trunk_idx.size(); ++t)

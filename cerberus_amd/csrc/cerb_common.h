@@ -81,13 +81,13 @@ struct HeadParams {
     const float* w2q;    // W2 for head_group_kernel<true> (4x4x1 matrix instructions): [set 2][blk 6][64 lane][r 4] = W2[4 set + (l & 3)][16 blk + 4 (l >> 4) + r]
     const float* b2;     // [32] (padded)
     int N, H, W;
-    int out_ch;          // 3 or 7 (<= 8)
-    int kind;            // 0 = INST (write softmax ch 1..2 as float2), 1 = TYPE (write argmax)
+    int out_ch;          // 2, 3 or 7 (<= 8)
+    int kind;            // 0 = INST (write softmax ch 1..out_ch-1: a float2, or one float of a two-class head), 1 = TYPE (write argmax)
     int crop_y0, crop_x0, out_h, out_w;   // centre crop window in tile coordinates
     int roi;             // 1: only the pixel blocks that overlap the crop window are computed (logits must be NULL)
     int rows, row0, xa0, nxb;  // set by the launcher: the kernel walks 16-pixel blocks (n, row0 + r, xa0 + 16 xb), r < rows, xb < nxb
     float* logits;       // optional [N][H][W][out_ch] NHWC (tests)
-    float* out_inst;     // kind 0: float [..][2]
+    float* out_inst;     // kind 0: float [..][out_ch - 1]
     unsigned char* out_type_u8;  // kind 1, optional
     long long* out_type_i64;     // kind 1, optional
     const long long* tile_off;   // optional per-tile element offset (in pixels) into the destination canvas

@@ -489,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd2_kernel(Bwd2Params p) {
 
 hipError_t cerb_launch_slab_sum(const float* part, float* out, int n, int blocks, int groups, hipStream_t st);
 
-bool cerb_head_train_supported(long long rows, int cin, int chid, int out) { return cin == PC && chid == HC && (out == 3 || out == 7) && rows > 0 && rows % 64 == 0; }
+bool cerb_head_train_supported(long long rows, int cin, int chid, int out) { return cin == PC && chid == HC && (out == 2 || out == 3 || out == 7) && rows > 0 && rows % 64 == 0; }
 
 // hid [rows][96] = prev [rows][64] W1^T + b1; bn_part: [*bn_blocks][96][2] doubles for cerb_launch_bn_finalize (rows of one group)
 // in_bn (optional): {mean, rstd, gamma, beta} [64] of the BatchNorm in FRONT of the head -- `prev` is then its raw input (see the kernel)
@@ -543,7 +543,8 @@ void cerb_bn_bwd_finalize_launch(const double* partial, int C, int blocks, float
 hipError_t cerb_launch_head_bwd1(const float* hid, const float* dlog, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* w2,
                                  float* dw2, float* db2, float* dgamma, float* dbeta, long long rows, int out, void* ws, hipStream_t st) {
     const HeadBwdWs w = head_ws(ws, rows, out);
-    if (out == 3) hipLaunchKernelGGL((head_bwd1_kernel<3>), dim3(w.blocks1), dim3(256), 0, st, hid, dlog, mean, rstd, gamma, beta, w2, w.pw, w.pb, w.pbn, rows, B1_ROWS);
+    if (out == 2) hipLaunchKernelGGL((head_bwd1_kernel<2>), dim3(w.blocks1), dim3(256), 0, st, hid, dlog, mean, rstd, gamma, beta, w2, w.pw, w.pb, w.pbn, rows, B1_ROWS);  // two-class INST head (IP-ERODED-*)
+    else if (out == 3) hipLaunchKernelGGL((head_bwd1_kernel<3>), dim3(w.blocks1), dim3(256), 0, st, hid, dlog, mean, rstd, gamma, beta, w2, w.pw, w.pb, w.pbn, rows, B1_ROWS);
     else if (out == 7) hipLaunchKernelGGL((head_bwd1_kernel<7>), dim3(w.blocks1), dim3(256), 0, st, hid, dlog, mean, rstd, gamma, beta, w2, w.pw, w.pb, w.pbn, rows, B1_ROWS);
     else return hipErrorInvalidValue;
     (void)cerb_launch_slab_sum(w.pw, dw2, out * HC, w.blocks1, 1, st);
@@ -564,8 +565,14 @@ hipError_t cerb_launch_head_bwd2(const float* hid, const float* dlog, const floa
     p.dprev = dprev; p.part_w1 = w.pw1; p.part_b1 = w.pb1; p.rows = rows; p.inv_m = eval_mode ? 0.f : 1.f / (float)rows; p.assign = assign;
     const int blocks = (int)std::min<long long>(rows / 64, B2_BLOCKS);
     constexpr size_t LDS_BYTES = (size_t)(64 * DS + 64 * PS_ + HC * PC + 64 * 8) * 4;  // 69.6 KB: two workgroups per CU
-    static bool attr3[64], attr7[64];
-    if (out == 3) {
+    static bool attr2[64], attr3[64], attr7[64];
+    if (out == 2) {
+        if (cerb_attr_needed(attr2)) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_bwd2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((head_bwd2_kernel<2>), dim3(blocks), dim3(256), LDS_BYTES, st, p);
+    } else if (out == 3) {
         if (cerb_attr_needed(attr3)) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_bwd2_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
             if (e != hipSuccess) return e;

@@ -587,7 +587,9 @@ __global__ __launch_bounds__(256, 2) void head_kernel(HeadParams p) {
     }
     if (!inside) continue;
     const long long dst = (p.tile_off ? p.tile_off[n] : (long long)n * p.tile_stride) + (long long)cy * p.row_stride + cx;
-    if (p.kind == 0) {
+    if (p.kind == 0 && p.out_ch == 2) {  // two-class INST head (IP-ERODED-*): one probability per pixel, the canvas pixel stride follows the head
+        p.out_inst[dst] = ex[1] / sum;
+    } else if (p.kind == 0) {
         float2 o;
         o.x = ex[1] / sum;
         o.y = ex[2] / sum;
@@ -840,7 +842,9 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
         }
         if (!inside) continue;
         const long long dst = (p.tile_off ? p.tile_off[n] : (long long)n * p.tile_stride) + (long long)cy * p.row_stride + cx;
-        if (p.kind == 0) {
+        if (p.kind == 0 && p.out_ch == 2) {  // two-class INST head (IP-ERODED-*): one probability per pixel, the canvas pixel stride follows the head
+            p.out_inst[dst] = ex[1] / sum;
+        } else if (p.kind == 0) {
             float2 o;
             o.x = ex[1] / sum;
             o.y = ex[2] / sum;

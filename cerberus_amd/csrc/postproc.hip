@@ -2337,6 +2337,16 @@ __global__ void gl_threshold_kernel(const float* __restrict__ inst, long long ro
         fg[p] = (s[0] - c) > thr;
     }
 }
+// PostProcInstErodedMap (loader/postproc.py:147-242): the map is the ONE inner-probability channel of a two-class INST head, fg = inner > 0.5
+__global__ void er_threshold_kernel(const float* __restrict__ inner, long long row_stride, int pix_stride, int H, int W, uint8_t* __restrict__ fg) {
+    const long long n = (long long)H * W;
+    const double invW = 1.0 / (double)W;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        int y, x;
+        pix_yx(p, W, invW, y, x);
+        fg[p] = inner[y * row_stride + (long long)x * pix_stride] > 0.5f;
+    }
+}
 struct Box {
     int y1, y2, x1, x2;
 };
@@ -2759,8 +2769,9 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
     return 0;
 }
 
+// one_channel: the eroded-map scheme (cerb_postproc_eroded) -- `inst` holds the inner probability alone and `thr` is not used
 static int gland_lumen(const float* inst, int H, int W, long long row_stride, int pix_stride, float thr, int min_size, int ksize,
-                       int32_t* labels_out, int32_t* n_inst_out, void* ws, size_t ws_bytes, hipStream_t st, const char* who) {
+                       int32_t* labels_out, int32_t* n_inst_out, void* ws, size_t ws_bytes, hipStream_t st, const char* who, bool one_channel = false) {
     if (!inst || !labels_out || !ws || H <= 0 || W <= 0) return cerb_set_error(std::string(who) + ": bad arguments");
     if (ws_bytes < cerb_pp_workspace_bytes(H, W)) return cerb_set_error(std::string(who) + ": workspace too small");
     if ((long long)H * W >= (1ll << 31)) return cerb_set_error(std::string(who) + ": map too large (H*W must be < 2^31)");
@@ -2790,7 +2801,8 @@ static int gland_lumen(const float* inst, int H, int W, long long row_stride, in
     if (!cB) return cerb_set_error(std::string(who) + ": workspace carve failed");
     const unsigned g = grid_for(n);
 
-    hipLaunchKernelGGL(gl_threshold_kernel, dim3(g), dim3(256), 0, st, inst, row_stride, pix_stride, H, W, thr, fg);
+    if (one_channel) hipLaunchKernelGGL(er_threshold_kernel, dim3(g), dim3(256), 0, st, inst, row_stride, pix_stride, H, W, fg);
+    else hipLaunchKernelGGL(gl_threshold_kernel, dim3(g), dim3(256), 0, st, inst, row_stride, pix_stride, H, W, thr, fg);
     PP_OK(hipMemsetAsync(area, 0, (size_t)n * 4, st));
     if (ccl_run(fg, 1, L, H, W, st, area)) return 1;
     hipLaunchKernelGGL(ccl_keep_roots_kernel, dim3(g), dim3(256), 0, st, L, area, min_size, flag, n);
@@ -2800,7 +2812,15 @@ static int gland_lumen(const float* inst, int H, int W, long long row_stride, in
     PP_OK(hipMemsetAsync(labels_out, 0, (size_t)n * 4, st));
     int n_inst = 0;  // the one host round trip of this path: 4 bytes of metadata (number of instances)
     PP_OK(hipMemcpyAsync(&n_inst, small, 4, hipMemcpyDeviceToHost, st));
+    int area0 = 0;   // pixels of the component rooted at pixel 0 (a component's root is its first pixel in raster order)
+    if (one_channel) PP_OK(hipMemcpyAsync(&area0, area, 4, hipMemcpyDeviceToHost, st));
     PP_OK(hipStreamSynchronize(st));
+    if (one_channel && area0 == n) {
+        // PostProcInstErodedMap walks `np.unique(inst_lab).tolist()[1:]` (loader/postproc.py:160): the smallest label is dropped as "the background".  A map
+        // without one background pixel is one component with id 1 -- that id is what gets dropped, and the reference returns an empty map.
+        n_inst = 0;
+        PP_OK(hipMemsetAsync(small, 0, 4, st));
+    }
     if (n_inst_out) PP_OK(hipMemcpyAsync(n_inst_out, small, 4, hipMemcpyDeviceToDevice, st));
     if (n_inst == 0) return 0;
     if (n_inst + 1 > max_inst) return cerb_set_error(std::string(who) + ": internal: instance table overflow");
@@ -2819,14 +2839,22 @@ static int gland_lumen(const float* inst, int H, int W, long long row_stride, in
     Spans se;
     ellipse_spans(ksize, &se);
     int first = 1, rc = 0;
+    // coff is a 32-bit running sum over ALL crops (the kernels index a batch relative to coff[first]): thousands of small instances with a padded
+    // box each (nuclei at min_size 8) must still fit it
+    long long crop_sum = 0;
+    for (int i = 1; i <= n_inst; ++i) crop_sum += (long long)h_area[i];
+    if (crop_sum >= (1ll << 31)) {
+        rc = cerb_set_error(std::string(who) + ": the instance crops of this map add up to 2^31 pixels or more");
+        first = n_inst + 1;
+    }
     while (first <= n_inst) {
         int last = first;
         size_t tot = (size_t)h_area[first];
-        if (tot > crop_cap) {
+        if (tot > crop_cap || tot >= (1ull << 31)) {
             rc = cerb_set_error(std::string(who) + ": one instance crop exceeds the workspace");
             break;
         }
-        while (last + 1 <= n_inst && tot + (size_t)h_area[last + 1] <= crop_cap) tot += (size_t)h_area[++last];
+        while (last + 1 <= n_inst && tot + (size_t)h_area[last + 1] <= crop_cap && tot + (size_t)h_area[last + 1] < (1ull << 31)) tot += (size_t)h_area[++last];
         const int cnt = last - first + 1;
         const int tot_i = (int)tot;
         const unsigned gb = grid_for(tot_i);
@@ -2854,6 +2882,15 @@ extern "C" int cerb_postproc_lumen(const float* inst, int H, int W, long long ro
                                    int32_t* n_inst_out, void* ws, size_t ws_bytes, void* hip_stream) {
     return gland_lumen(inst, H, W, row_stride, pix_stride, 0.5f, (int)(150.0 * ((double)ds * (double)ds)), (int)(2.0 * (double)ds), labels_out,
                        n_inst_out, ws, ws_bytes, (hipStream_t)hip_stream, "cerb_postproc_lumen");
+}
+// PostProcInstErodedMap (loader/postproc.py:147-265, the IP-ERODED-3 / -11 codes): threshold 0.5 on the inner map, remove_small_objects, then the gland
+// scheme above for all three tissues -- nuclei included, with the 3 x 3 element.  No ds_factor: the reference's `scale` argument is never read.
+extern "C" int cerb_postproc_eroded(const float* inner, int H, int W, long long row_stride, int pix_stride, int tissue, int32_t* labels_out,
+                                    int32_t* n_inst_out, void* ws, size_t ws_bytes, void* hip_stream) {
+    static const int min_size[3] = {1500, 150, 8}, ksize[3] = {11, 3, 3};  // Gland, Lumen, Nuclei (postproc.py:151-156, :183-188, :215-220)
+    if (tissue < 0 || tissue > 2) return cerb_set_error("cerb_postproc_eroded: tissue must be 0 (Gland), 1 (Lumen) or 2 (Nuclei)");
+    return gland_lumen(inner, H, W, row_stride, pix_stride, 0.5f, min_size[tissue], ksize[tissue], labels_out, n_inst_out, ws, ws_bytes,
+                       (hipStream_t)hip_stream, "cerb_postproc_eroded", true);
 }
 extern "C" int cerb_mask_lumen_by_gland(int32_t* lumen, const int32_t* gland, long long n_pix, void* hip_stream) {
     if (!lumen || !gland || n_pix < 0) return cerb_set_error("cerb_mask_lumen_by_gland: bad arguments");

@@ -628,7 +628,8 @@ class NetDesc(torch.nn.Module):
     # ---- device-resident output wrapper (softmax / crop / argmax fused into the head kernels) ---------------
     def infer_tiles(self, tiles_u8, output_shape, head_name_list=None, type_dtype=torch.int64):
         """F7 of SURVEY.md par.8a on device: returns OrderedDict head-key -> CUDA tensor
-        ('*-INST' (N,oh,ow,2) float32; '*-TYPE' (N,oh,ow) int64|uint8; 'Patch-Class' (N,oh,ow) float32)."""
+        ('*-INST' (N,oh,ow,out_ch-1) float32 -- 2 channels for a 3-class head, 1 for a 2-class one; '*-TYPE' (N,oh,ow) int64|uint8;
+        'Patch-Class' (N,oh,ow) float32)."""
         if not isinstance(output_shape, (list, tuple)):
             output_shape = [output_shape, output_shape]
         oh, ow = int(output_shape[0]), int(output_shape[1])
@@ -642,7 +643,7 @@ class NetDesc(torch.nn.Module):
                 outs.append(None)
                 continue
             if hname == "INST":
-                t = torch.empty((n, oh, ow, 2), dtype=torch.float32, device=tiles_u8.device)
+                t = torch.empty((n, oh, ow, och - 1), dtype=torch.float32, device=tiles_u8.device)
             elif hname == "TYPE":
                 t = torch.empty((n, oh, ow), dtype=type_dtype, device=tiles_u8.device)
             else:

@@ -34,7 +34,7 @@ def register_net(model):
 
 @torch.library.custom_op("cerberus_amd::infer_tiles", mutates_args=(), device_types="cuda")
 def infer_tiles(tiles: torch.Tensor, handle: int, out_h: int, out_w: int, heads: str) -> list[torch.Tensor]:
-    """heads: comma-separated head keys ('Nuclei-INST,Nuclei-TYPE'), '' = all in model order.  INST -> float32 [N, oh, ow, 2],
+    """heads: comma-separated head keys ('Nuclei-INST,Nuclei-TYPE'), '' = all in model order.  INST -> float32 [N, oh, ow, out_ch - 1],
     TYPE -> int64 [N, oh, ow], Patch-Class -> float32 [N, oh, ow]."""
     m = _nets.get(int(handle))
     if m is None:
@@ -52,7 +52,7 @@ def infer_tiles(tiles: torch.Tensor, handle: int, out_h: int, out_w: int, heads:
         if key not in want:
             outs.append(None)
             continue
-        t = torch.empty((n, out_h, out_w, 2) if hname == "INST" else (n, out_h, out_w), dtype=torch.int64 if hname == "TYPE" else torch.float32,
+        t = torch.empty((n, out_h, out_w, och - 1) if hname == "INST" else (n, out_h, out_w), dtype=torch.int64 if hname == "TYPE" else torch.float32,
                         device=tiles.device)
         outs.append(t)
         res[key] = t
@@ -65,10 +65,11 @@ def _(tiles, handle, out_h, out_w, heads):
     m = _nets.get(int(handle))
     want = [h for h in heads.split(",") if h] or ([d[3] for d in m._decoders] if m is not None else [])
     n = tiles.shape[0]
+    och = {d[3]: d[2] for d in m._decoders} if m is not None else {}
     out = []
     for h in want:
         if h.endswith("INST"):
-            out.append(tiles.new_empty((n, out_h, out_w, 2), dtype=torch.float32))
+            out.append(tiles.new_empty((n, out_h, out_w, och.get(h, 3) - 1), dtype=torch.float32))
         elif h.endswith("TYPE"):
             out.append(tiles.new_empty((n, out_h, out_w), dtype=torch.int64))
         else:

@@ -1,10 +1,12 @@
-"""Mirror of the reference's instance post-processing (loader/postproc.py:268-407) on top of the HIP kernels.
+"""Mirror of the reference's instance post-processing (loader/postproc.py:147-407) on top of the HIP kernels.
 
     PostProcInstErodedContourMap.post_process(raw_map, idx_dict, tissue_mode, ds_factor=1.0) -> (inst_map, type_map)
+    PostProcInstErodedMap.post_process(raw_map, idx_dict, tissue_mode, scale=1.0) -> (inst_map, type_map)
 
-keeps the reference's signature, assertions and return dtypes (int32 for the nuclei watershed branch, float64
-otherwise) when called with numpy arrays.  The device-resident entry points used by the tile / WSI drivers are
-`postproc_device` (one INST map -> int32 label map, all on the GPU) and `mask_lumen_by_gland`.
+keep the reference's signatures, assertions and return dtypes (contour maps: int32 for the nuclei watershed branch, float64
+otherwise; eroded maps: float64 for all three tissues) when called with numpy arrays.  The device-resident entry points used by
+the tile / WSI drivers are `postproc_device` (one three-class INST map -> int32 label map, all on the GPU), `postproc_eroded_device`
+(the same for the one-channel map of a two-class INST head) and `mask_lumen_by_gland`.
 
 Handles are not picklable, so this runs in the main process (the reference's nr_post_proc_workers=0 path,
 infer/tile.py:413-416).  There is no CPU fallback.
@@ -70,6 +72,33 @@ def postproc_device(inst, tissue_mode, ds_factor=1.0, out=None, exact_ties=True)
     return labels, {"n_inst": meta[0], "n_ambiguous": meta[1]}
 
 
+ERODED_TISSUE = {"GLAND": 0, "LUMEN": 1, "NUCLEI": 2}  # the `tissue` argument of cerb_postproc_eroded
+
+
+def postproc_eroded_device(inner, tissue_mode, out=None):
+    """PostProcInstErodedMap (loader/postproc.py:147-242; the IP-ERODED-3 / -11 codes) on the device.
+    inner: CUDA float32 (H,W) or (H,W,1) tensor -- the one probability channel of a two-class INST head -- or a strided window of a canvas.
+    Returns (labels int32 CUDA (H,W), info) with info = {'n_inst': 0-d CUDA int32}.  Threshold 0.5, remove_small_objects (1500 / 150 / 8 pixels
+    for Gland / Lumen / Nuclei), then per instance: padded crop, dilation (11 / 3 / 3 ellipse), fill holes, paste -- for nuclei too."""
+    if not torch.cuda.is_available():
+        raise _lib.CerberusHipError("cerberus_amd needs a ROCm GPU; there is no CPU fallback")
+    assert tissue_mode.upper() in ERODED_TISSUE, tissue_mode
+    assert inner.is_cuda and inner.dtype == torch.float32 and (inner.dim() == 2 or (inner.dim() == 3 and inner.shape[2] == 1))
+    h, w = int(inner.shape[0]), int(inner.shape[1])
+    dev = inner.device
+    labels = out if out is not None else torch.empty((h, w), dtype=torch.int32, device=dev)
+    assert labels.is_contiguous() and labels.dtype == torch.int32 and tuple(labels.shape) == (h, w)
+    meta = torch.zeros(2, dtype=torch.int32, device=dev)
+    if h == 0 or w == 0:
+        return labels, {"n_inst": meta[0]}
+    ws = _workspace(dev, h, w)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().cerb_postproc_eroded(inner.data_ptr(), h, w, inner.stride(0), inner.stride(1), ERODED_TISSUE[tissue_mode.upper()],
+                                                   labels.data_ptr(), meta.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(stream)))
+    return labels, {"n_inst": meta[0]}
+
+
 def mask_lumen_by_gland(lumen, gland):
     """Lumen *= (Gland > 0)   (infer/tile.py:187-191) in place on the GPU."""
     assert lumen.is_cuda and gland.is_cuda and lumen.dtype == torch.int32 and gland.dtype == torch.int32
@@ -111,6 +140,31 @@ class PostProcInstErodedContourMap(object):
             inst_map = inst_map.astype(np.float64)
         return inst_map, type_map
 
+class PostProcInstErodedMap(object):
+    """Drop-in for the reference class of the same name (loader/postproc.py:147-265): the post-processing of the IP-ERODED-3 / -11 codes."""
+
+    last_info = None
+
+    @classmethod
+    def post_process(cls, raw_map, idx_dict, tissue_mode, scale=1.0):
+        # `scale` is accepted and never read, as in the reference (:245-257: __func(inst_fg) runs the full-resolution parameters whatever it is)
+        assert tissue_mode.upper() in ERODED_TISSUE
+        tissue_ch = "%s-INST" % tissue_mode
+        assert tissue_ch in list(idx_dict.keys())
+        is_np = isinstance(raw_map, np.ndarray)
+        dev_map = torch.from_numpy(np.ascontiguousarray(raw_map, dtype=np.float32)).cuda() if is_np else raw_map
+        inst_fg = dev_map[..., idx_dict[tissue_ch][0]: idx_dict[tissue_ch][1]]
+        assert inst_fg.shape[-1] == 1, "PostProcInstErodedMap reads the one inner channel of a two-class INST head"
+        labels, info = postproc_eroded_device(inst_fg, tissue_mode)
+        cls.last_info = info
+        type_ch = tissue_mode + "-" + "TYPE"
+        if type_ch in list(idx_dict.keys()):
+            type_map = raw_map[..., idx_dict[type_ch][0]: idx_dict[type_ch][1]]  # NOT squeezed (:259-263), unlike the contour class
+        else:
+            type_map = None
+        if not is_np:
+            return labels, type_map
+        return labels.cpu().numpy().astype(np.float64), type_map  # np.zeros([h, w]) canvases: float64 for every tissue (:159, :191, :223)
 
 
 def inst_table_device(inst_map, type_map=None, n_inst=None):

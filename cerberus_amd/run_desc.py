@@ -14,7 +14,7 @@ def infer_step(img_list, model, output_shape, head_name_list):
     output_shape    int or [h, w] -- centre crop applied to every dense head (cropping_center, misc/utils.py:94-104)
     head_name_list  decoder names (`model_args["considered_tasks"]`, infer/base.py:52)
     returns         list (one per sample) of dict head-key -> numpy array:
-                    '*-INST' (oh,ow,2) float32, '*-TYPE' (oh,ow) int64, 'Patch-Class' (oh,ow) float32
+                    '*-INST' (oh,ow,out_ch-1) float32 (2 channels, or 1 for a two-class head), '*-TYPE' (oh,ow) int64, 'Patch-Class' (oh,ow) float32
 
     The whole of forward + softmax + channel slice + crop + argmax runs in the HIP kernels; the only host work
     left is the final .cpu().numpy() the reference also does (run_desc.py:492).

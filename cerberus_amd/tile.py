@@ -14,6 +14,8 @@ Different by design (MI355X-first):
   * post-processing runs in the main process (GPU handles are not picklable) -- the reference's
     nr_post_proc_workers=0 path.
 Not implemented (SURVEY.md par.8f "next" rows): contour tracing (cv2.findContours) and the overlay jpg.
+Post-processing is chosen per tissue from decoder_dict["<Tissue>-INST"]: IP-ERODED-CONTOUR-* (three-class head, two canvas channels,
+PostProcInstErodedContourMap) or IP-ERODED-* (two-class head, one canvas channel, PostProcInstErodedMap); a model may mix them.
 """
 import math
 import os
@@ -24,10 +26,12 @@ import numpy as np
 import torch
 
 from .net_desc import create_model
-from .postproc import get_inst_info_dict, mask_lumen_by_gland, postproc_device
+from .postproc import get_inst_info_dict, mask_lumen_by_gland, postproc_device, postproc_eroded_device
 from .run_desc import infer_step
 
-POSTPROC_CODES = ("IP-ERODED-CONTOUR-3", "IP-ERODED-CONTOUR-11")  # -> PostProcInstErodedContourMap (infer/tile.py:35-40)
+CONTOUR_CODES = ("IP-ERODED-CONTOUR-3", "IP-ERODED-CONTOUR-11")  # -> PostProcInstErodedContourMap (infer/tile.py:35-40): three-class INST heads
+ERODED_CODES = ("IP-ERODED-3", "IP-ERODED-11")                   # -> PostProcInstErodedMap: two-class INST heads, one inner channel
+POSTPROC_CODES = CONTOUR_CODES + ERODED_CODES
 
 
 def _pad_reflect_numpy1(img, pads):
@@ -224,7 +228,7 @@ class InferManager(object):
         canv = OrderedDict()
         for name, hname, och, key in net._decoders:
             if hname == "INST":
-                canv[key] = torch.zeros((row0[-1], wmax, 2), dtype=torch.float32, device=dev)
+                canv[key] = torch.zeros((row0[-1], wmax, och - 1), dtype=torch.float32, device=dev)  # the head's own channel count
             elif hname == "TYPE":
                 canv[key] = torch.zeros((row0[-1], wmax), dtype=torch.uint8, device=dev)
             else:
@@ -251,8 +255,14 @@ class InferManager(object):
                 code = self.decoder_dict.get(tissue + "-INST") if getattr(self, "decoder_dict", None) else "IP-ERODED-CONTOUR-3"
                 if tissue + "-INST" in raw:
                     if code not in POSTPROC_CODES:
-                        raise NotImplementedError("post-proc code %r: only IP-ERODED-CONTOUR-* (PostProcInstErodedContourMap) is on the HIP path" % code)
-                    inst[tissue], pp_info[tissue] = postproc_device(raw[tissue + "-INST"], tissue)
+                        raise NotImplementedError("post-proc code %r: only %s are on the HIP path" % (code, ", ".join(POSTPROC_CODES)))
+                    nch = int(raw[tissue + "-INST"].shape[2])
+                    if nch != (1 if code in ERODED_CODES else 2):
+                        raise ValueError("%s-INST: post-proc code %r reads %d channel(s), the model's head gives %d" % (tissue, code, 1 if code in ERODED_CODES else 2, nch))
+                    if code in ERODED_CODES:  # per tissue: a model may mix the two schemes (infer/tile.py:168-186 looks the class up per tissue)
+                        inst[tissue], pp_info[tissue] = postproc_eroded_device(raw[tissue + "-INST"], tissue)
+                    else:
+                        inst[tissue], pp_info[tissue] = postproc_device(raw[tissue + "-INST"], tissue)
                     types[tissue] = raw.get(tissue + "-TYPE")
                 elif tissue == "Patch-class":
                     pclass = raw.get("Patch-Class")

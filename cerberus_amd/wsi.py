@@ -163,6 +163,23 @@ def check_shardable(slide_hw, patch_output_shape, world_size):
         raise ValueError("slide of %d patch rows cannot be sharded over %d ranks: use at most %d" % (rows, world_size, rows))
 
 
+ERODED_CODES = ("IP-ERODED-3", "IP-ERODED-11")  # PostProcInstErodedMap (infer/wsi.py:51-56): tile mode only here (cerberus_amd/tile.py)
+
+
+def refuse_eroded_codes(decoder_dict=None, net=None):
+    """The slide drivers' band / halo ownership rules are those of the contour scheme (PostProcInstErodedContourMap): a model whose INST heads
+    carry the IP-ERODED-3 / -11 codes -- two classes, ONE canvas channel -- is refused by name before a canvas exists.  decoder_dict:
+    settings.yml's req_target_code; net: a NetDesc (a two-class INST head is such a head whatever the settings say)."""
+    for key, code in (decoder_dict or {}).items():
+        if key.endswith("-INST") and code in ERODED_CODES:
+            raise NotImplementedError("%s: post-proc code %r (PostProcInstErodedMap) runs in tile mode only (run_infer_tile.py); the slide driver "
+                                      "implements IP-ERODED-CONTOUR-3 / -11" % (key, code))
+    for name, hname, och, key in (net._decoders if net is not None else []):
+        if hname == "INST" and int(och) == 2:
+            raise NotImplementedError("%s: a two-class INST head (post-proc codes IP-ERODED-3 / IP-ERODED-11, PostProcInstErodedMap) runs in tile mode "
+                                      "only (run_infer_tile.py); the slide driver implements IP-ERODED-CONTOUR-3 / -11" % key)
+
+
 class WSIRunner(object):
     """One per process / GPU.  (Single-process simulations of more ranks than patch rows get empty bands; distributed drivers call
     check_shardable first.)"""
@@ -170,6 +187,7 @@ class WSIRunner(object):
     def __init__(self, net, slide_hw, patch_input_shape=256, patch_output_shape=256, batch_size=32, rank=0, world_size=1, patch_sel=None, twin=None, row_range=None):
         """twin: a second handle with the same parameters (NetDesc.twin()); batches then alternate between the two on two side streams.
         row_range: (r0, r1) patch rows instead of rank's band of the world -- the sub-bands of cerberus_amd.stream_bands (slides larger than HBM)."""
+        refuse_eroded_codes(net=net)  # before any canvas is allocated
         self.net = net
         self.twin = twin
         self._side = None

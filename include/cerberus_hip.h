@@ -33,7 +33,8 @@ const char* cerb_last_error(void);
  * decoder_names[i]  e.g. "Lumen","Gland","Nuclei","Nuclei#TYPE","Gland#TYPE","Patch-Class"  (decoder_kwargs order,
  *                   already filtered by considered_tasks, models/net_desc.py:61-63)
  * head_names[i]     "INST" | "TYPE" | "OUT"        (an output head of that decoder)
- * out_ch[i]         number of output channels of that head (3,3,3,7,3,9 in models/paramset.yml:46-60)
+ * out_ch[i]         number of output channels of that head (3,3,3,7,3,9 in models/paramset.yml:46-60).  An INST head has 3 (inner, contour: the
+ *                   IP-ERODED-CONTOUR-* targets) or 2 (inner alone: the IP-ERODED-* targets) channels; TYPE heads 2..8; anything else is refused.
  * One entry per OUTPUT HEAD.  A decoder with several heads (models/net_desc.py:81-87: `{"Gland": {"INST": 3, "TYPE": 3}}` builds one decoder
  * trunk and a ModuleDict of heads over it, :196-198) is listed once per head, the decoder name repeated: the trunk's convolutions are loaded and
  * run ONCE, every head reads its features; out[] / logits[] of cerb_forward_io stay per entry.  (Inference only: a train-packed handle refuses it.)
@@ -56,7 +57,8 @@ int cerb_net_finalize(cerb_net* net);
  * row_stride -- the stitching of infer/tile.py:141-163 (outputs can be written straight into a slide canvas).
  *
  * For decoder i (same order as cerb_net_create):
- *   INST head : out[i] -> float  [..][2]   softmax channels 1..2        (run_desc.py:452-455)
+ *   INST head : out[i] -> float  [..][out_ch-1]  softmax channels 1..out_ch-1: [2] for a 3-class head, [1] for a 2-class one (run_desc.py:452-455);
+ *               the destination's pixel stride follows the head, the addressing below stays in pixels
  *   TYPE head : out[i] -> int64 or uint8 class id (argmax of softmax)   (run_desc.py:490-491), see type_is_u8
  *   OUT  head : out[i] -> float class id broadcast over out_h x out_w   (Patch-Class, run_desc.py:480-487)
  * Destination addressing (in pixels): tile n, row y, col x  ->  (tile_off ? tile_off[n] : n*tile_stride)
@@ -167,6 +169,15 @@ int cerb_postproc_gland(const float* inst, int h, int w, long long row_stride, i
                         int32_t* labels_out, int32_t* n_inst_out, void* ws, size_t ws_bytes, void* hip_stream);
 int cerb_postproc_lumen(const float* inst, int h, int w, long long row_stride, int pix_stride, float ds_factor,
                         int32_t* labels_out, int32_t* n_inst_out, void* ws, size_t ws_bytes, void* hip_stream);
+/* PostProcInstErodedMap.post_process (loader/postproc.py:147-265; the IP-ERODED-3 / -11 codes of infer/tile.py:35-40) for a two-class INST head.
+ * inner : device float, ONE probability per pixel (`pix_stride` 1 for a packed map), row_stride / labels_out / n_inst_out / ws as above.
+ * tissue: 0 Gland, 1 Lumen, 2 Nuclei.  fg = inner > 0.5; remove_small_objects(min_size 1500 / 150 / 8); 4-connected labels in raster order; per id
+ * ascending: bounding box padded by 2 * ksize (ksize 11 / 3 / 3) on each side only where the padded edge stays inside, dilation by the ksize x ksize
+ * ellipse inside that crop, holes filled inside that crop, pasted (later ids overwrite).  Nuclei take this scheme too -- no watershed.  There is no
+ * ds_factor: the reference's `scale` argument is never read.  A map without a single background pixel comes back empty, as in the reference (its id list
+ * `np.unique(inst_lab)[1:]` drops the smallest label, which is then the one instance). */
+int cerb_postproc_eroded(const float* inner, int h, int w, long long row_stride, int pix_stride, int tissue, int32_t* labels_out,
+                         int32_t* n_inst_out, void* ws, size_t ws_bytes, void* hip_stream);
 /* Lumen *= (Gland > 0)   (infer/tile.py:187-191, infer/wsi.py:799-804) */
 int cerb_mask_lumen_by_gland(int32_t* lumen_labels, const int32_t* gland_labels, long long n_pix, void* hip_stream);
 

@@ -107,7 +107,7 @@ def main(argv=None):
 
     from cerberus_amd.tile import InferManager
     from cerberus_amd.weights import DEFAULT_REQ_TARGET_CODE, default_model_kwargs
-    from cerberus_amd.wsi import DatWriter, SlabUploader, WSIRunner, check_shardable, collect_wsi_inst_arrays, synth_slide, wsi_meta
+    from cerberus_amd.wsi import DatWriter, SlabUploader, WSIRunner, check_shardable, collect_wsi_inst_arrays, refuse_eroded_codes, synth_slide, wsi_meta
 
     dist, watch = None, launch.null_watch()
     n_dev = max(1, torch.cuda.device_count())
@@ -136,6 +136,7 @@ def main(argv=None):
         with open(os.path.join(args["--model"], "settings.yml")) as fh:
             settings = yaml.full_load(fh)
         decoders, model_args = settings["dataset_kwargs"]["req_target_code"], settings["model_kwargs"]
+    refuse_eroded_codes(decoders)  # IP-ERODED-3 / -11 models: tile mode only -- said by name before the model is loaded or a canvas allocated
     if (args["--wsi_file_ext"] or "").lower() in (".tif", ".tiff", ".svs"):  # tiled files: their tile-decode worker processes start underneath the model's loading
         from cerberus_amd.reader import warm_decode_workers
 
