@@ -20,7 +20,7 @@ SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip
 # The translation units that read developer A/B switches (cerb_common.h: cerb_dev_getenv).  The product library compiles them WITHOUT the switches
 # (every one folds to its default); the same units compiled with -DCERB_DEV_SWITCHES, linked with the other units' objects, make
 # libcerberus_hip_dev.so -- loaded only by the A/B tests' child processes (CERB_DEV_LIB=1, cerberus_amd/_lib.py).
-DEV_SOURCES = ["cerb_api.hip", "cerb_train.hip", "postproc.hip", "conv_wino4b.hip", "train_kernels.hip"]
+DEV_SOURCES = ["cerb_api.hip", "cerb_train.hip", "postproc.hip", "conv_wino4b.hip", "train_kernels.hip", "net_kernels.hip"]
 # Linked into libcerberus_hip_dev.so ONLY: the test-only entry layer (cerb_dev_* wrappers over single launchers of cerb_net.h, for tests/dev_kernels.py).
 # The product library neither compiles nor exports them (tests/test_abi.py).
 DEV_ONLY_SOURCES = ["dev_entry.hip"]

@@ -647,32 +647,38 @@ hipError_t cerb_launch_head(const HeadParams& p_in, hipStream_t st) {
 struct HeadGroupParams {
     HeadParams h[8];
     int n_heads;
+    int generic;  // developers' library only (CERB_HEAD_GENERIC=1): every head takes the generic body
 };
+// ReLU of a matrix-instruction result in ONE instruction.  fmaxf() compiles to a pair: a canonicalising v_max v, v, v in front of the maximum, because
+// the compiler cannot see that a matrix instruction never returns a signalling NaN (48 extra VALU instructions per task).  Same result for every input
+// a matrix instruction can produce: NaN -> 0, +-Inf and finite values as fmaxf (tests/test_head_group_diet_gpu.py).  volatile: the 48 of a task stay in
+// program order behind GEMM1's last scheduling barrier, so the ones that read the last matrix instructions' results come dozens of instructions later.
+__device__ __forceinline__ float head_relu(float v) {
+    float r;
+    asm volatile("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
 // W2_44 (round 4, the default): the second 1x1 (96 -> 3 / 7 logits) on v_mfma_f32_4x4x1_16B_f32 instead of a 16-row matrix instruction whose
 // rows 3 (7) .. 15 multiply zeros: 16 independent 4x4 outer products per instruction, block b = lanes 4b .. 4b+3 = four pixels of one k-slot
 // group, B = the lane's own hidden value (exactly where the first GEMM left it), A = W2[out l & 3][the block's hidden channel], D = 4 logits per
 // lane, partial over the lane's k-slot group; 24 instructions of 2 passes per pixel block and set of 4 logits (48 for the 7-class head) replace
 // 24 of 8 passes, then two cross-lane exchanges sum the four k-slot groups.  Matrix-pipe time of a 32-pixel task: 7680 -> 6528 (6912) cycles.
-template <bool W2_44>
-__global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupParams gp) {
-    __shared__ __attribute__((aligned(16))) float s_w1[6 * 4 * 64 * 4];
-    __shared__ __attribute__((aligned(16))) float s_w2[(W2_44 ? 2 : 1) * 6 * 64 * 4];  // W2_44: w2q = [set][blk][lane][r], else w2p = [blk][lane][r]
-    __shared__ __attribute__((aligned(16))) float s_b1[96];
-    __shared__ __attribute__((aligned(16))) float s_b2[32];
-    const HeadParams& p = gp.h[blockIdx.y];
+//
+// The task loop of one workgroup (= one head), specialised on the head's shape: <OUT_CH, KIND> = <2, 0> <3, 0> (INST) and <3, 1> <7, 1> (TYPE) do only
+// what that head needs -- no second set of 4 logits (its matrix instructions, LDS reads and exchanges) below 5 classes, max / expf / sum / division
+// over OUT_CH terms, block positions stepped along the wave's consecutive tasks instead of divided out, one-instruction ReLU.  OUT_CH == 0 is the
+// generic body: every width up to 8 at run time and the `logits` side output (and W2_44 == false, round 3's kernel).  The specialised bodies
+// leave out only work whose result is never used (the dropped softmax terms are + 0.f on a non-negative sum): the outputs are bit-identical.
+template <bool W2_44, int OUT_CH, int KIND>
+__device__ __forceinline__ void head_group_body(const HeadParams& p, const float* s_w1, const float* s_w2, const float* s_b1, const float* s_b2) {
+    constexpr bool GEN = OUT_CH == 0;
+    constexpr int NL = GEN ? 8 : OUT_CH;  // logits a lane finishes
+    static_assert(GEN || W2_44, "the specialised bodies are written for the 4x4x1 second GEMM");
     const int tid = threadIdx.x, lane = tid & 63, px = lane & 15, ks = lane >> 4;
-    {
-        const f32x4h* w1g = reinterpret_cast<const f32x4h*>(p.w1p);
-        const f32x4h* w2g = reinterpret_cast<const f32x4h*>(W2_44 ? p.w2q : p.w2p);
-        for (int i = tid; i < 6 * 4 * 64; i += 256) reinterpret_cast<f32x4h*>(s_w1)[i] = w1g[i];
-        for (int i = tid; i < (W2_44 ? 2 : 1) * 6 * 64; i += 256) reinterpret_cast<f32x4h*>(s_w2)[i] = w2g[i];
-        if (tid < 96) s_b1[tid] = p.b1[tid];
-        if (tid < 32) s_b2[tid] = p.b2[tid];
-    }
-    __syncthreads();
     const f32x4h* w1v = reinterpret_cast<const f32x4h*>(s_w1) + lane;
     const f32x4h* w2v = reinterpret_cast<const f32x4h*>(s_w2) + lane;
-    const bool wide = p.out_ch > 4;  // W2_44: a second set of 4 logits
+    const int out_ch = GEN ? p.out_ch : OUT_CH;
+    const bool wide = GEN ? p.out_ch > 4 : OUT_CH > 4;  // W2_44: a second set of 4 logits
     const unsigned nblk = (unsigned)p.N * (unsigned)p.rows * (unsigned)p.nxb;  // 16-pixel blocks (launcher: < 2^31)
     const unsigned ntask = (nblk + 1u) >> 1;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane(tid >> 6);
@@ -691,6 +697,16 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
         r.row = (int)(q - (unsigned)r.n * (unsigned)p.rows);
         return r;
     };
+    auto inc = [&](BPos b) {  // wave-uniform: the block after b, as decode() of the next index (the one past the last block is n == N too)
+        if (++b.xb == p.nxb) {
+            b.xb = 0;
+            if (++b.row == p.rows) {
+                b.row = 0;
+                ++b.n;
+            }
+        }
+        return b;
+    };
     // NHWC: a pixel's 64 channels are contiguous (group stride 16 floats); tile-planar (conv_wino4p.hip's output): a pixel's 16-channel groups
     // are one plane = 4096 floats apart, and the 16 pixels of a row segment are four runs of 256 bytes
     const int gstride = p.feat_planar ? 4096 : 16;
@@ -700,15 +716,24 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
         return p.feat + (((long long)n * p.H + y) * p.W + x) * 64 + 4 * ks;
     };
     f32x4h xn[4][2];
-    auto request = [&](unsigned t) {
+    auto request_at = [&](const BPos& b, int pb) {
+        const float* fp = ptr_of(b);
 #pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-            const float* fp = ptr_of(decode(2u * t + (unsigned)pb));
-#pragma unroll
-            for (int g = 0; g < 4; ++g) xn[g][pb] = *reinterpret_cast<const f32x4h*>(fp + gstride * g);
-        }
+        for (int g = 0; g < 4; ++g) xn[g][pb] = *reinterpret_cast<const f32x4h*>(fp + gstride * g);
     };
-    request(task);
+    auto request = [&](unsigned t) {
+        request_at(decode(2u * t), 0);
+        request_at(decode(2u * t + 1u), 1);
+    };
+    BPos nb[2] = {};  // specialised bodies: the two blocks of the task whose features are in flight
+    if constexpr (GEN) {
+        request(task);
+    } else {
+        nb[0] = decode(2u * task);
+        nb[1] = inc(nb[0]);
+        request_at(nb[0], 0);
+        request_at(nb[1], 1);
+    }
     float amax = 0.f;  // largest |logit| this lane has finished (head_absmax_commit)
 #pragma unroll 1
     for (; task < task_end; ++task) {
@@ -717,7 +742,17 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
         for (int g = 0; g < 4; ++g)
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb) x[g][pb] = xn[g][pb];
-        if (task + 1 < task_end) request(task + 1);  // a whole task ahead of its use
+        const BPos cb0 = nb[0], cb1 = nb[1];
+        if (task + 1 < task_end) {  // a whole task ahead of its use
+            if constexpr (GEN) {
+                request(task + 1);
+            } else {
+                nb[0] = inc(cb1);
+                nb[1] = inc(nb[0]);
+                request_at(nb[0], 0);
+                request_at(nb[1], 1);
+            }
+        }
         f32x4h acc1[6][2];
 #pragma unroll
         for (int blk = 0; blk < 6; ++blk) {
@@ -751,7 +786,7 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) acc1[blk][pb][r] = fmaxf(acc1[blk][pb][r], 0.f);
+                for (int r = 0; r < 4; ++r) acc1[blk][pb][r] = GEN ? fmaxf(acc1[blk][pb][r], 0.f) : head_relu(acc1[blk][pb][r]);
         float lg[8];
         if constexpr (W2_44) {
             f32x4h lo[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, hi[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -778,17 +813,21 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
             const bool odd = ks & 1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float mine = odd ? lo[1][e] : lo[0][e];
-                mine += __shfl_xor(odd ? lo[0][e] : lo[1][e], 16);
-                mine += __shfl_xor(mine, 32);
-                lg[e] = mine + s_b2[e];
-                float mh = 0.f;
-                if (wide) {
-                    mh = odd ? hi[1][e] : hi[0][e];
-                    mh += __shfl_xor(odd ? hi[0][e] : hi[1][e], 16);
-                    mh += __shfl_xor(mh, 32);
+                if (e < NL) {
+                    float mine = odd ? lo[1][e] : lo[0][e];
+                    mine += __shfl_xor(odd ? lo[0][e] : lo[1][e], 16);
+                    mine += __shfl_xor(mine, 32);
+                    lg[e] = mine + s_b2[e];
                 }
-                lg[4 + e] = mh + s_b2[4 + e];
+                if (4 + e < NL) {
+                    float mh = 0.f;
+                    if (wide) {
+                        mh = odd ? hi[1][e] : hi[0][e];
+                        mh += __shfl_xor(odd ? hi[0][e] : hi[1][e], 16);
+                        mh += __shfl_xor(mh, 32);
+                    }
+                    lg[4 + e] = mh + s_b2[4 + e];
+                }
             }
         } else {
         f32x4h acc2[2];
@@ -816,46 +855,56 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
         }
         }
         if (ks >= 2) continue;
-        const BPos bp = decode(2u * task + (unsigned)ks);
+        BPos bp;
+        if constexpr (GEN) {
+            bp = decode(2u * task + (unsigned)ks);
+        } else {
+            bp.n = ks ? cb1.n : cb0.n;
+            bp.row = ks ? cb1.row : cb0.row;
+            bp.xb = ks ? cb1.xb : cb0.xb;
+        }
         const int n = bp.n, y_ = bp.row + p.row0, x_ = p.xa0 + 16 * bp.xb + px;
         if (2u * task + (unsigned)ks >= nblk || x_ >= p.W) continue;
-        if (p.logits) {
-            const long long P = ((long long)n * p.H + y_) * p.W + x_;
-            for (int e = 0; e < p.out_ch; ++e) p.logits[P * p.out_ch + e] = lg[e];
+        if constexpr (GEN) {
+            if (p.logits) {
+                const long long P = ((long long)n * p.H + y_) * p.W + x_;
+                for (int e = 0; e < p.out_ch; ++e) p.logits[P * p.out_ch + e] = lg[e];
+            }
         }
         float mx = lg[0];
 #pragma unroll
-        for (int e = 1; e < 8; ++e)
-            if (e < p.out_ch) mx = fmaxf(mx, lg[e]);
-        float ex[8], sum = 0.f;
+        for (int e = 1; e < NL; ++e)
+            if (e < out_ch) mx = fmaxf(mx, lg[e]);
+        float ex[NL], sum = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            ex[e] = (e < p.out_ch) ? expf(lg[e] - mx) : 0.f;
+        for (int e = 0; e < NL; ++e) {
+            ex[e] = (e < out_ch) ? expf(lg[e] - mx) : 0.f;
             sum += ex[e];
         }
         const int cy = y_ - p.crop_y0, cx = x_ - p.crop_x0;
         const bool inside = cy >= 0 && cy < p.out_h && cx >= 0 && cx < p.out_w;
-        if (inside || p.logits) {  // (a cropped forward only finishes the kept window's features: pixels of the 16-aligned cover outside it do not count)
+        if (inside || (GEN && p.logits)) {  // (a cropped forward only finishes the kept window's features: pixels of the 16-aligned cover outside it do not count)
 #pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (e < p.out_ch) amax = fmaxf(amax, fabsf(lg[e]));
+            for (int e = 0; e < NL; ++e)
+                if (e < out_ch) amax = fmaxf(amax, fabsf(lg[e]));
         }
         if (!inside) continue;
         const long long dst = (p.tile_off ? p.tile_off[n] : (long long)n * p.tile_stride) + (long long)cy * p.row_stride + cx;
-        if (p.kind == 0 && p.out_ch == 2) {  // two-class INST head (IP-ERODED-*): one probability per pixel, the canvas pixel stride follows the head
+        const int kind = GEN ? p.kind : KIND;
+        if (kind == 0 && out_ch == 2) {  // two-class INST head (IP-ERODED-*): one probability per pixel, the canvas pixel stride follows the head
             p.out_inst[dst] = ex[1] / sum;
-        } else if (p.kind == 0) {
+        } else if (kind == 0) {
             float2 o;
             o.x = ex[1] / sum;
-            o.y = ex[2] / sum;
+            o.y = ex[NL > 2 ? 2 : 0] / sum;
             *reinterpret_cast<float2*>(p.out_inst + dst * 2) = o;
         } else {
             int best = 0;
             float bv = ex[0] / sum;
 #pragma unroll
-            for (int e = 1; e < 8; ++e) {
+            for (int e = 1; e < NL; ++e) {
                 const float pe = ex[e] / sum;
-                if (e < p.out_ch && pe > bv) {
+                if (e < out_ch && pe > bv) {
                     bv = pe;
                     best = e;
                 }
@@ -867,11 +916,48 @@ __global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupPa
     if (p.absmax_bits) head_absmax_commit(p.absmax_bits, amax);
 }
 
+template <bool W2_44>
+__global__ __launch_bounds__(256, HEAD_G_OCC) void head_group_kernel(HeadGroupParams gp) {
+    __shared__ __attribute__((aligned(16))) float s_w1[6 * 4 * 64 * 4];
+    __shared__ __attribute__((aligned(16))) float s_w2[(W2_44 ? 2 : 1) * 6 * 64 * 4];  // W2_44: w2q = [set][blk][lane][r], else w2p = [blk][lane][r]
+    __shared__ __attribute__((aligned(16))) float s_b1[96];
+    __shared__ __attribute__((aligned(16))) float s_b2[32];
+    const HeadParams& p = gp.h[blockIdx.y];
+    // workgroup-uniform: which body serves this head (the generic one: other widths, the `logits` side output, the developers' A/B switch)
+    const bool generic = !W2_44 || gp.generic || p.logits != nullptr;
+    const int shape = generic ? 0 : p.kind * 8 + p.out_ch;
+    const bool spec = shape == 2 || shape == 3 || shape == 8 + 3 || shape == 8 + 7;
+    {
+        const int tid = threadIdx.x;
+        const f32x4h* w1g = reinterpret_cast<const f32x4h*>(p.w1p);
+        const f32x4h* w2g = reinterpret_cast<const f32x4h*>(W2_44 ? p.w2q : p.w2p);
+        const int w2n = (W2_44 && !(spec && p.out_ch <= 4) ? 2 : 1) * 6 * 64;  // a specialised body of at most 4 classes never reads the second set
+        for (int i = tid; i < 6 * 4 * 64; i += 256) reinterpret_cast<f32x4h*>(s_w1)[i] = w1g[i];
+        for (int i = tid; i < w2n; i += 256) reinterpret_cast<f32x4h*>(s_w2)[i] = w2g[i];
+        if (tid < 96) s_b1[tid] = p.b1[tid];
+        if (tid < 32) s_b2[tid] = p.b2[tid];
+    }
+    __syncthreads();
+    if constexpr (W2_44) {
+        if (shape == 2) return head_group_body<true, 2, 0>(p, s_w1, s_w2, s_b1, s_b2);
+        if (shape == 3) return head_group_body<true, 3, 0>(p, s_w1, s_w2, s_b1, s_b2);
+        if (shape == 8 + 3) return head_group_body<true, 3, 1>(p, s_w1, s_w2, s_b1, s_b2);
+        if (shape == 8 + 7) return head_group_body<true, 7, 1>(p, s_w1, s_w2, s_b1, s_b2);
+    }
+    head_group_body<W2_44, 0, 0>(p, s_w1, s_w2, s_b1, s_b2);
+}
+
 hipError_t cerb_launch_head_group(const HeadParams* heads, int n_heads, hipStream_t st, int w2_44) {
     if (n_heads < 1 || n_heads > 8) return hipErrorInvalidValue;
 
     HeadGroupParams gp = {};
     gp.n_heads = n_heads;
+#ifdef CERB_DEV_SWITCHES
+    {  // developer A/B, read at every launch: the generic body for every head (tests/test_head_group_diet_gpu.py compares the two in one process)
+        const char* e = cerb_dev_getenv("CERB_HEAD_GENERIC");
+        gp.generic = e && e[0] != '0';
+    }
+#endif
     unsigned max_blocks = 0;
     for (int i = 0; i < n_heads; ++i) {
         HeadParams p = heads[i];
