@@ -45,6 +45,9 @@ WSI_OPTIONS = _COMMON + [
     ("--jpeg_decode", True, "host", "(not in the reference) host | device: where the JPEG tiles of .svs / tiled TIFF slides are decoded -- host: PIL / libjpeg, tile by "
                                     "tile (unless CERB_JPEG_DECODE says otherwise); device: native Huffman pass on the host, inverse DCT / up-sampling / colour in HIP "
                                     "kernels, the same bytes (sets CERB_JPEG_DECODE=device; cerberus_amd/jpeg_device.py)"),
+    ("--auto_mask", False, False, "(not in the reference's command line) generate the tissue mask of every slide on the device from a thumbnail -- the reference's "
+                                  "get_tissue_mask (misc/utils.py:195-244; cerberus_amd/tissue.py) -- and use it like a --msk_dir mask; not together with --msk_dir"),
+    ("--auto_mask_ds", True, "16", "(not in the reference) with --auto_mask: the thumbnail is the slide at 1/<n> of the processing resolution"),
 ]
 
 

@@ -229,6 +229,32 @@ int cerb_pclass_tissue_map(const float* pclass, long long row_stride, int h, int
 int cerb_label_mask(const uint8_t* mask, long long row_stride, int h, int w, int32_t* labels_out, int32_t* n_out,
                     void* ws, size_t ws_bytes, void* hip_stream);
 
+/* ---- tissue mask of a slide thumbnail: misc/utils.py:195-244 (stain_entropy_otsu, morphology, get_tissue_mask) on the device ------------------
+ * The reference's docstring promises a generated mask when none is supplied (infer/wsi.py:509); this is the routine behind that promise.  Every
+ * call is ordered on hip_stream, allocates nothing and synchronises nothing; ws / ws_bytes: caller-owned device workspace of at least
+ * cerb_tissue_workspace_bytes(h, w) bytes, 8-byte aligned.  h * w < 2^31.  Host arithmetic (the two tables, Otsu on 256 counts) is
+ * cerberus_amd/tissue.py's.
+ *   cerb_tissue_hed        misc/utils.py:198-199, (rgb2hed(img) * 255).astype(uint8): rgb uint8 [h][w][3] with row_stride bytes between rows ->
+ *                          planes_out uint8 [3][h][w] (H, E, D).  lut: double [3][256][3] = [channel][value][stain], the per-channel logarithm times
+ *                          the stain matrix; byte = trunc(((lut[0][r] + lut[1][g]) + lut[2][b]) * 255) modulo 256.
+ *   cerb_tissue_entropy    misc/utils.py:203-208, rank.entropy(plane, disk(4)) of the three planes and (H + E) - D: ent_out double [h][w];
+ *                          pixels outside the image are left out of the count; term_table: double [50][50], [pop][count] =
+ *                          (count / pop) * log(count / pop) / log(2), summed in ascending bin order.  minmax_out: device double[2], the minimum and
+ *                          maximum of ent_out (no floating-point atomics: per-block values folded by a second kernel).
+ *   cerb_tissue_histogram  misc/utils.py:210, the histogram behind threshold_otsu: counts256_out int64[256] = np.histogram(ent, 256, (min, max))
+ *                          by numpy's assignment rule against edges257 = np.linspace(min, max, 257) (device doubles).  Integer counts.
+ *   cerb_tissue_threshold  misc/utils.py:211: mask_out uint8 [h][w] = ent > thr.
+ *   cerb_tissue_morphology misc/utils.py:216-235: scipy binary_erosion by disk(3) (outside the image counts as clear), remove_small_holes(2000),
+ *                          remove_small_objects(2000), scipy binary_dilation by disk(3), remove_small_holes(2000), binary_fill_holes; 4-connected.
+ *                          mask_in / mask_out: uint8 [h][w], packed; out is 0 / 1. */
+size_t cerb_tissue_workspace_bytes(int h, int w);
+int cerb_tissue_hed(const uint8_t* rgb, long long row_stride, int h, int w, const double* lut, uint8_t* planes_out, void* hip_stream);
+int cerb_tissue_entropy(const uint8_t* planes, int h, int w, const double* term_table, double* ent_out, double* minmax_out, void* ws,
+                        size_t ws_bytes, void* hip_stream);
+int cerb_tissue_histogram(const double* ent, int h, int w, const double* edges257, int64_t* counts256_out, void* hip_stream);
+int cerb_tissue_threshold(const double* ent, int h, int w, double thr, uint8_t* mask_out, void* hip_stream);
+int cerb_tissue_morphology(const uint8_t* mask_in, int h, int w, uint8_t* mask_out, void* ws, size_t ws_bytes, void* hip_stream);
+
 /* ---- instance table: the segmented reductions of get_inst_info_dict (loader/postproc.py:12-75) on the device --------
  * labels: int32 label map (row stride in elements); type_map: optional uint8 class map (NULL = none).
  * table : device int64 [n_inst][16], row id-1 = {area, sum_x, sum_y, y1, y2 (exclusive), x1, x2 (exclusive), first,

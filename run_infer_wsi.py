@@ -6,7 +6,8 @@ labelled on the device, and only the instance dictionary is written -- `dat/<sli
 (infer/wsi.py:844-853 there).  Flag names and defaults are the reference's (cerberus_amd/cli.py); the tiling / cache flags it
 parses and then overrides with constants are accepted and ignored.  `--msk_dir` tissue masks are honoured: patches without
 tissue do not run, the Patch-Class map is masked, gland / lumen are labelled per tissue region (cerberus_amd/tissue.py); every
-slide also gets `tissue/<slide>.mat` (infer/wsi.py:688-716).
+slide also gets `tissue/<slide>.mat` (infer/wsi.py:688-716).  `--auto_mask` makes that mask on the device instead, from a thumbnail of the slide at
+1/`--auto_mask_ds` of the processing resolution (the reference's get_tissue_mask, misc/utils.py:195-244); everything after it is the `--msk_dir` path.
 
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N run_infer_wsi.py ...`; patch rows shard into one
 contiguous band per rank, inference needs no collective, post-processing is band-local (cerberus_amd/shard_postproc.py)."""
@@ -83,9 +84,39 @@ def _open_slide(path, proc_mpp):
     return reader.rows(proc_mpp, "mpp"), h, w, 0, reader
 
 
+def _slide_list(args):
+    """The slides of this run: the directory's files with the extension, those with a mask under --msk_dir (run_infer_wsi.py:76-83 there), the
+    reference's batch-of-slides window."""
+    ext = args["--wsi_file_ext"]
+    slides = sorted(glob.glob(os.path.join(args["--input_dir"], "*" + ext))) if args["--input_dir"] else []
+    if args["--msk_dir"]:
+        slides = [p for p in slides if os.path.isfile(os.path.join(args["--msk_dir"], _basename(p, ext) + ".png"))]
+    step, bulk = int(args["--wsi_proc_step"]), int(args["--wsi_bulk_idx"])
+    return slides[(bulk - 1) * step: bulk * step]
+
+
+def _check_auto_mask(args):
+    """--auto_mask is refused, before a slide is opened or a device touched, where it cannot mean anything: beside --msk_dir (two masks), and for a
+    `synthetic:<H>x<W>:<seed>` spec, which has no reader to take a thumbnail from (its pixels only ever exist on the device, band by band)."""
+    if not args["--auto_mask"]:
+        return
+    if args["--msk_dir"]:
+        raise ValueError("--auto_mask and --msk_dir are both given: a slide's tissue mask is either generated or read from <msk_dir>/<slide>.png, not both")
+    try:
+        ds = int(args["--auto_mask_ds"])
+    except ValueError:
+        ds = 0
+    if ds < 1:
+        raise ValueError("--auto_mask_ds takes a whole number >= 1, got %r" % (args["--auto_mask_ds"],))
+    for p in _slide_list(args):
+        if os.path.splitext(p)[1].lower() == ".txt":
+            raise ValueError("--auto_mask: %s is a synthetic slide spec (`synthetic:<H>x<W>:<seed>`): it has no reader to take a thumbnail from" % os.path.basename(p))
+
+
 def main(argv=None):
     args = parse("run_infer_wsi.py", WSI_OPTIONS, argv, version="CoBi Gland Inference")
     require_model(args)
+    _check_auto_mask(args)
     if args["--jpeg_decode"] not in ("host", "device"):
         sys.exit("--jpeg_decode takes host or device, got %r" % args["--jpeg_decode"])
     if args["--jpeg_decode"] == "device":  # (before the ranks are started: they inherit it)
@@ -148,12 +179,9 @@ def main(argv=None):
     twin = None
 
     ext = args["--wsi_file_ext"]
-    slides = sorted(glob.glob(os.path.join(args["--input_dir"], "*" + ext))) if args["--input_dir"] else []
-    step, bulk = int(args["--wsi_proc_step"]), int(args["--wsi_bulk_idx"])  # the reference's batch-of-slides window
     msk_dir = args["--msk_dir"]
-    if msk_dir:  # only slides that have a mask are considered (run_infer_wsi.py:76-83 there)
-        slides = [p for p in slides if os.path.isfile(os.path.join(msk_dir, _basename(p, ext) + ".png"))]
-    slides = slides[(bulk - 1) * step: bulk * step]
+    auto_mask = bool(args["--auto_mask"])
+    slides = _slide_list(args)  # under --msk_dir only slides that have a mask are considered (run_infer_wsi.py:76-83 there)
     print("Number of WSIs in list:", len(slides))
     win, out, batch = int(args["--patch_input_shape"]), int(args["--patch_output_shape"]), int(args["--batch_size"])
     writer = tissue_writer = None
@@ -188,11 +216,27 @@ def main(argv=None):
         if min(H, W) < 4:  # (the quarter-resolution tissue map and the half-resolution gland maps have no pixels: the reference dies in cv2.resize there)
             raise ValueError("%s is %d x %d pixels at the processing resolution: nothing to segment" % (base, H, W))
         mask, sel, regions = None, None, None
-        if msk_dir:
-            from cerberus_amd.tissue import TissueRegions, load_mask, select_patches
+        if msk_dir or auto_mask:
+            from cerberus_amd.tissue import TissueRegions, get_tissue_mask, load_mask, select_patches, thumbnail
             from cerberus_amd.wsi import SlideGeometry
 
-            mask = load_mask(os.path.join(msk_dir, base + ".png"))
+            if msk_dir:
+                mask = load_mask(os.path.join(msk_dir, base + ".png"))
+            else:
+                # every rank computes the mask from the same thumbnail with the same integer / table arithmetic: the same mask, no collective
+                t_m = time.perf_counter()
+                thumb = thumbnail(reader, float(args["--wsi_proc_mag"]), "mpp", int(args["--auto_mask_ds"]))
+                try:
+                    mask = get_tissue_mask(torch.from_numpy(thumb).cuda()).cpu().numpy()
+                except ValueError as e:  # nothing to threshold: skipped like a slide without a mask file under --msk_dir
+                    if rank == 0:
+                        print("Skip %s: %s" % (base, e))
+                    if log:
+                        log.warning("Skip %s- no tissue mask: %s" % (base, e))
+                        _close_logger(log)
+                    continue
+                if log:
+                    log.info("Tissue Mask Time: {0} ({1} x {2} thumbnail, {3} tissue pixels)".format(time.perf_counter() - t_m, thumb.shape[0], thumb.shape[1], int(mask.sum())))
             sel = select_patches(mask, SlideGeometry((H, W), win, out).out_boxes(), (H, W))
             if rank == 0 and args["--save_mask"]:
                 from PIL import Image
