@@ -10,7 +10,7 @@ EXPORTS = [
     "cerb_net_finalize", "cerb_net_forward", "cerb_net_flops", "cerb_device_bytes_held", "cerb_pp_workspace_bytes", "cerb_postproc_nuclei",
     "cerb_postproc_gland", "cerb_postproc_lumen", "cerb_postproc_eroded", "cerb_mask_lumen_by_gland", "cerb_event_create",
     "cerb_event_record", "cerb_event_elapsed_ms", "cerb_event_destroy", "cerb_net_profile_enable",
-    "cerb_net_profile_count", "cerb_net_profile_get", "cerb_net_set_conv_algo", "cerb_net_set_head_algo", "cerb_net_set_planar", "cerb_net_set_packed_items", "cerb_net_set_crop_roi", "cerb_net_set_fold_bn", "cerb_net_set_bn_eval", "cerb_net_begin_reload", "cerb_net_update_params", "cerb_net_forward_train", "cerb_net_train_grads", "cerb_net_grad_lookup", "cerb_copy_d2d", "cerb_adam_step", "cerb_adam_step_multi", "cerb_synth_slide", "cerb_gather_patches", "cerb_downsample2_inst", "cerb_half_size", "cerb_downsample2_inst_region", "cerb_pclass_tissue_map", "cerb_resample_box", "cerb_resample_area", "cerb_label_mask", "cerb_inst_table", "cerb_relabel", "cerb_head_loss_workspace_bytes", "cerb_head_loss", "cerb_head_loss_wmap", "cerb_inst_contour_start", "cerb_inst_contour_start_workspace_bytes", "cerb_inst_contour_count", "cerb_inst_contour_points",
+    "cerb_net_profile_count", "cerb_net_profile_get", "cerb_net_set_conv_algo", "cerb_net_set_head_algo", "cerb_net_set_planar", "cerb_net_set_packed_items", "cerb_net_set_crop_roi", "cerb_net_set_fold_bn", "cerb_net_set_bn_eval", "cerb_net_begin_reload", "cerb_net_update_params", "cerb_net_forward_train", "cerb_net_train_grads", "cerb_net_grad_lookup", "cerb_copy_d2d", "cerb_adam_step", "cerb_adam_step_multi", "cerb_synth_slide", "cerb_gather_patches", "cerb_downsample2_inst", "cerb_half_size", "cerb_downsample2_inst_region", "cerb_downsample2_map", "cerb_downsample2_map_region", "cerb_pclass_tissue_map", "cerb_resample_box", "cerb_resample_area", "cerb_label_mask", "cerb_inst_table", "cerb_relabel", "cerb_head_loss_workspace_bytes", "cerb_head_loss", "cerb_head_loss_wmap", "cerb_inst_contour_start", "cerb_inst_contour_start_workspace_bytes", "cerb_inst_contour_count", "cerb_inst_contour_points",
     "cerb_target_workspace_bytes", "cerb_target_window_workspace_bytes", "cerb_target_element", "cerb_target_pixel_maps", "cerb_target_eroded_maps",
     "cerb_target_weight_maps",
     "cerb_valid_stats_bytes", "cerb_valid_stats_reset", "cerb_valid_stats_accumulate",
@@ -150,6 +150,9 @@ def lib():
     L.cerb_half_size.argtypes = [C.c_int]
     L.cerb_downsample2_inst_region.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                                C.c_void_p, C.c_void_p]
+    L.cerb_downsample2_map.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_downsample2_map_region.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int,
+                                              C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_pclass_tissue_map.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_label_mask.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cerb_head_loss_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]

@@ -49,6 +49,15 @@ WSI_OPTIONS = _COMMON + [
                                   "get_tissue_mask (misc/utils.py:195-244; cerberus_amd/tissue.py) -- and use it like a --msk_dir mask; not together with --msk_dir"),
     ("--auto_mask_ds", True, "16", "(not in the reference) with --auto_mask: the thumbnail is the slide at 1/<n> of the processing resolution"),
 ]
+# WSI_OPTIONS is pinned, entry by entry, by tests/test_tissue_mask_host.py and is closed: every NEW run_infer_wsi.py option goes into WSI_MODEL_OPTIONS
+# below (appended at its end), and run_infer_wsi.py parses WSI_ALL_OPTIONS = WSI_OPTIONS + WSI_MODEL_OPTIONS.
+WSI_MODEL_OPTIONS = [
+    ("--eroded_maps", False, False, "(not in the reference's command line) run a model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, PostProcInstErodedMap) "
+                                    "on slides: one-channel canvases, the eroded labelling inside the band / halo / ownership protocol; without the flag such a "
+                                    "model is refused by name.  Not with --reference_tiling when the Nuclei head is such a head; slides that would need sub-band "
+                                    "streaming are refused"),
+]
+WSI_ALL_OPTIONS = WSI_OPTIONS + WSI_MODEL_OPTIONS
 
 
 def usage(prog, options):

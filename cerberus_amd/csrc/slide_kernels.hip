@@ -75,6 +75,10 @@ __global__ void gather_patches_kernel(const uint8_t* __restrict__ slide, long lo
 // samples 2d and 2d+1 with weights (.5, .5); where 2d >= n - 1 (odd n, last output) the weights are (1, 0).  With a region
 // (infer/wsi.py:742-776) every source sample is first multiplied by [region_lab[nearest(sy, sx)] == region_id], the nearest
 // mapping being cv2.resize(INTER_NEAREST)'s min(floor(s * mh / h), mh - 1).
+// NCH: channels read from every source pixel and written per output pixel (2: inner + contour of a three-class INST head, 1: the one map of a
+// two-class head).  The arithmetic of a plane does not depend on NCH, so plane c of a one-channel call is bit-equal to plane c of a two-channel
+// one; a one-channel call touches one float per source pixel and writes ho * wo floats, densely (lane i -> dst[p0 + i]).
+template <int NCH>
 __global__ void downsample2_inst_kernel(const float* __restrict__ src, long long row_stride, int pix_stride, int h, int w, int ho, int wo,
                                         const int* __restrict__ region_lab, long long lab_row_stride, int mh, int mw, int region_id,
                                         float* __restrict__ dst) {
@@ -98,10 +102,10 @@ __global__ void downsample2_inst_kernel(const float* __restrict__ src, long long
         const float* b = src + (long long)y1 * row_stride;
         const long long o0 = (long long)x0 * pix_stride, o1 = (long long)x1 * pix_stride;
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
+        for (int c = 0; c < NCH; ++c) {
             const float top = (a[o0 + c] * m00) * wx0 + (a[o1 + c] * m01) * wx1;
             const float bot = (b[o0 + c] * m10) * wx0 + (b[o1 + c] * m11) * wx1;
-            dst[p * 2 + c] = top * wy0 + bot * wy1;
+            dst[p * NCH + c] = top * wy0 + bot * wy1;
         }
     }
 }
@@ -148,18 +152,34 @@ extern "C" int cerb_gather_patches(const uint8_t* slide, long long h, long long 
 }
 static int half_size(int n) { return (int)lrint(n * 0.5); }  // cvRound
 extern "C" int cerb_half_size(int n) { return half_size(n); }
-extern "C" int cerb_downsample2_inst_region(const float* src, long long row_stride, int pix_stride, int h, int w, const int32_t* region_lab,
-                                            long long lab_row_stride, int mh, int mw, int region_id, float* dst, void* hip_stream) {
-    if (!src || !dst || h < 1 || w < 1 || (region_lab && (mh < 1 || mw < 1))) return cerb_set_error("cerb_downsample2_inst: bad arguments");
+template <int NCH>
+static int downsample2_launch(const char* who, const float* src, long long row_stride, int pix_stride, int h, int w, const int32_t* region_lab, long long lab_row_stride,
+                              int mh, int mw, int region_id, float* dst, void* hip_stream) {
+    if (!src || !dst || h < 1 || w < 1 || (region_lab && (mh < 1 || mw < 1))) return cerb_set_error(std::string(who) + ": bad arguments");
     const int ho = half_size(h), wo = half_size(w);
-    if (ho < 1 || wo < 1) return cerb_set_error("cerb_downsample2_inst: map too small");
-    hipLaunchKernelGGL(downsample2_inst_kernel, dim3(grid_for((long long)ho * wo)), dim3(256), 0, (hipStream_t)hip_stream, src, row_stride, pix_stride,
+    if (ho < 1 || wo < 1) return cerb_set_error(std::string(who) + ": map too small");
+    hipLaunchKernelGGL(downsample2_inst_kernel<NCH>, dim3(grid_for((long long)ho * wo)), dim3(256), 0, (hipStream_t)hip_stream, src, row_stride, pix_stride,
                        h, w, ho, wo, region_lab, lab_row_stride, region_lab ? mh : 1, region_lab ? mw : 1, region_id, dst);
     SK_CHECK();
     return 0;
 }
+extern "C" int cerb_downsample2_inst_region(const float* src, long long row_stride, int pix_stride, int h, int w, const int32_t* region_lab,
+                                            long long lab_row_stride, int mh, int mw, int region_id, float* dst, void* hip_stream) {
+    return downsample2_launch<2>("cerb_downsample2_inst", src, row_stride, pix_stride, h, w, region_lab, lab_row_stride, mh, mw, region_id, dst, hip_stream);
+}
 extern "C" int cerb_downsample2_inst(const float* src, long long row_stride, int pix_stride, int h, int w, float* dst, void* hip_stream) {
     return cerb_downsample2_inst_region(src, row_stride, pix_stride, h, w, nullptr, 0, 0, 0, 0, dst, hip_stream);
+}
+// the channel-count variants: n_ch = 2 is the call above, n_ch = 1 the map of a two-class INST head (dst[ho][wo][n_ch])
+extern "C" int cerb_downsample2_map_region(const float* src, long long row_stride, int pix_stride, int h, int w, int n_ch, const int32_t* region_lab,
+                                           long long lab_row_stride, int mh, int mw, int region_id, float* dst, void* hip_stream) {
+    if (n_ch != 1 && n_ch != 2) return cerb_set_error("cerb_downsample2_map: n_ch must be 1 or 2");
+    if (pix_stride < n_ch) return cerb_set_error("cerb_downsample2_map: pix_stride is smaller than n_ch");
+    if (n_ch == 1) return downsample2_launch<1>("cerb_downsample2_map", src, row_stride, pix_stride, h, w, region_lab, lab_row_stride, mh, mw, region_id, dst, hip_stream);
+    return downsample2_launch<2>("cerb_downsample2_map", src, row_stride, pix_stride, h, w, region_lab, lab_row_stride, mh, mw, region_id, dst, hip_stream);
+}
+extern "C" int cerb_downsample2_map(const float* src, long long row_stride, int pix_stride, int h, int w, int n_ch, float* dst, void* hip_stream) {
+    return cerb_downsample2_map_region(src, row_stride, pix_stride, h, w, n_ch, nullptr, 0, 0, 0, 0, dst, hip_stream);
 }
 extern "C" int cerb_pclass_tissue_map(const float* pclass, long long row_stride, int h, int w, const uint8_t* mask, long long mask_row_stride,
                                       int mh, int mw, float* dst, void* hip_stream) {

@@ -21,16 +21,61 @@ single GPU computes on the whole slide (up to the id bijection).  Choose margin 
 
 The phase functions are pure per-rank steps; `run_local` chains them for ranks simulated in one process (GPU test),
 `run_distributed` uses torch.distributed (RCCL on the GPU box, gloo in the CPU tests).  `label_fn` / `table_fn` default to the
-HIP kernels and fail loudly without a GPU; the gloo test injects numpy stand-ins to exercise the protocol itself."""
+HIP kernels and fail loudly without a GPU; the gloo test injects numpy stand-ins to exercise the protocol itself.
+
+One-channel windows (the canvas of a two-class INST head, post-proc codes IP-ERODED-3 / -11) go through the same protocol: `_device_label_fn` labels
+them with postproc_eroded_device (PostProcInstErodedMap: threshold, remove_small_objects, then per instance a padded crop, dilation, fill-holes and a
+paste), and everything after the labelling -- table, ownership by first pixel, publish / resolve, mask_by, owned_parts -- reads the OUTPUT label map
+alone.  Two properties make such a window's result the whole slide's:
+
+  * Overlap precedence.  Overlapping dilations are pasted in id order, so the later id wins the pixels both claim.  Ids are the raster order of the
+    CORES' first pixels (the labelling of the thresholded, size-filtered map), and a window is a row range of the slide: of any two cores that lie
+    in a window, the one that comes first in the window comes first on the slide.  The contested pixels therefore go to the same instance.
+  * Crop pad quirk.  The reference pads an instance's crop by pad = 2 * ksize on a side only when the padded side stays inside the map
+    (`y1 - pad >= 0 else y1`, `y2 + pad <= H - 1 else y2`; loader/postproc.py:166-171), so an artificial window edge changes the dilation of every
+    instance whose core lies within `pad` rows of it: core rows y1 <= pad - 1 at the top, y2 >= H - pad at the bottom.  The dilated instance holds
+    its core, so `guard >= 2 * ksize + 1` rows -- AT THE RESOLUTION OF THE LABELLED MAP: 23 for glands (ksize 11), 7 for lumina and nuclei (ksize 3)
+    -- puts every such instance into `cut`, and into n_truncated when it reaches the band.  BandState refuses a smaller guard for a one-channel
+    band with a ValueError that names the numbers (the default guard // 2 = 24 of the half-resolution tissues holds)."""
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 
-def _device_label_fn(window, tissue, ds_factor):
-    from .postproc import postproc_device
+# guard rows a one-channel (eroded-scheme) band needs, at the resolution of the labelled map: 2 * ksize + 1 (module docstring, "crop pad quirk")
+ERODED_MIN_GUARD = {"GLAND": 23, "LUMEN": 7, "NUCLEI": 7}
+# One labelling call of the eroded scheme fails by name when its instance crops add up to 2^31 pixels (cerb_postproc_eroded).  A nucleus crop is its
+# box padded by 6 px a side: a 20 x 20 px core box -> 32 x 32 = 1024 crop pixels.  At the 400-Mpx call size of run_infer_wsi.py that limit is reached
+# at 2^31 / 1024 / 400 = 5200 nuclei / Mpx -- tissue packed solid with nuclei has 3000 - 4000 -- so one-channel NUCLEI windows are held to a quarter
+# of max_band_px (100 Mpx: the limit is then at 21000 / Mpx, or at 84 x 84 px crops at 3000 / Mpx) wherever the map can be cut that small -- a
+# slide wider than 100 Mpx / (4 * margin) = 48800 px at the default margin keeps the full call size.  Where the bound is applied: one rank -- the
+# local bands of sharded_postprocess (run_infer_wsi.py sends a slide there when H * W exceeds THIS bound); several ranks -- bounded_label_fn on each
+# rank's window; check_eroded_nuclei_calls refuses a band that cannot be cut before its inference.  Gland / lumen windows are half-resolution maps
+# with a few thousand instances: a 400-Mpx window of 4000 glands would need 540000-pixel crops (730 x 730) to get there.
+ERODED_NUCLEI_CALL_SHARE = 4
 
+
+def eroded_max_band_px(max_band_px, tissue, n_ch, cols=0, margin=0):
+    """The per-call pixel bound of one tissue: max_band_px, or a quarter of it for a one-channel nuclei map (ERODED_NUCLEI_CALL_SHARE) -- unless a map
+    `cols` wide cannot be cut into bands that small with `margin` halo rows (local_band_count's condition: a band of two margins plus its halos), in
+    which case the full bound stands: a slide the contour scheme can band is never refused here, after its inference, for being wide."""
+    if max_band_px and int(n_ch) == 1 and tissue.upper() == "NUCLEI":
+        q = max(1, int(max_band_px) // ERODED_NUCLEI_CALL_SHARE)
+        if q // max(1, int(cols)) - 2 * int(margin) >= max(1, 2 * int(margin)):
+            return q
+    return max_band_px
+
+
+def _device_label_fn(window, tissue, ds_factor):
+    from .postproc import postproc_device, postproc_eroded_device
+
+    if window.dim() == 3 and int(window.shape[2]) == 1:
+        # one channel = PostProcInstErodedMap.  ds_factor is NOT passed on: the reference hands it over (infer/wsi.py:792-794) to a `scale` argument
+        # its class never reads (loader/postproc.py:245-257), so the half-resolution gland / lumen windows are labelled with the FULL-resolution
+        # parameters -- min_size 1500 / 150, the 11 x 11 / 3 x 3 element -- and so they are here
+        lab, info = postproc_eroded_device(window, tissue)
+        return lab, max(int(info["n_inst"].item()), 0)
     lab, info = postproc_device(window, tissue, ds_factor, exact_ties=False)  # WSI bands: see postproc_device
     n = int(info["n_inst"].item())
     return lab, max(n, 0)
@@ -75,11 +120,49 @@ def _device_mask_fn(lumen_window, gland_rows):
     mask_lumen_by_gland(lumen_window, gland_rows)
 
 
+def bounded_label_fn(label_fn, max_call_px, margin, guard, table_fn=None, relabel_fn=None):
+    """label_fn for a RANK's window (halo + band + halo) whose one-channel nuclei calls are held to eroded_max_band_px(max_call_px, ...) pixels: a
+    window above the bound is itself cut into local row bands and labelled through run_local -- the same halo / ownership / id protocol, nested --
+    so the window's label map has dense ids and the outer protocol goes on unchanged.  What the inner bands could not vouch for (their n_truncated +
+    n_unresolved) comes back as a third value, which BandState.label adds to the rank's n_truncated.  Everything else goes straight to label_fn."""
+    table_fn = table_fn or _device_table_fn
+    relabel_fn = relabel_fn or _device_relabel_fn
+
+    def fn(window, tissue, ds_factor):
+        if not max_call_px or window.dim() != 3 or int(window.shape[2]) != 1 or tissue.upper() != "NUCLEI":
+            return label_fn(window, tissue, ds_factor)
+        rows, cols = int(window.shape[0]), int(window.shape[1])
+        nb = local_band_count(rows, cols, eroded_max_band_px(max_call_px, tissue, 1, cols, margin), margin)
+        if nb == 1:
+            return label_fn(window, tissue, ds_factor)
+        cuts = [int(round(i * rows / nb)) for i in range(nb + 1)]
+        outs, n, infos = run_local([window[cuts[i]:cuts[i + 1]] for i in range(nb)], tissue, margin, guard, ds_factor, label_fn, table_fn, relabel_fn)
+        return assemble(outs), n, sum(i["n_truncated"] + i["n_unresolved"] for i in infos)
+
+    return fn
+
+
+def check_eroded_nuclei_calls(rows, cols, max_call_px, margin, world=1):
+    """Before a slide's inference: can the one-channel nuclei map of a rank -- `rows` band rows, plus the two halos when there are several ranks --
+    be labelled in calls of at most eroded_max_band_px(max_call_px, ...) pixels?  -> the number of calls' bands; local_band_count's ValueError
+    (a map too wide for row bands of that size) is raised HERE, by name, not after the inference."""
+    rows = int(rows) + (2 * int(margin) if int(world) > 1 else 0)
+    try:
+        return local_band_count(rows, int(cols), eroded_max_band_px(max_call_px, "Nuclei", 1, cols, margin), margin)
+    except ValueError as e:
+        raise ValueError("one-channel Nuclei-INST map (post-proc codes IP-ERODED-3 / -11, --eroded_maps) of %d x %d pixels: %s" % (rows, int(cols), e))
+
+
 class BandState(object):
     """Per-rank, per-tissue state carried between the phases."""
 
     def __init__(self, rank, world, band, y0_global, margin, guard, tissue, ds_factor=1.0, type_band=None):
-        assert band.dim() == 3 and band.shape[2] == 2, "band: (rows, W, 2) probability canvas of this rank"
+        assert band.dim() == 3 and band.shape[2] in (1, 2), "band: (rows, W, 2) probability canvas of this rank, or (rows, W, 1) of a two-class INST head"
+        if band.shape[2] == 1 and int(guard) < ERODED_MIN_GUARD[tissue.upper()]:
+            k = (ERODED_MIN_GUARD[tissue.upper()] - 1) // 2
+            raise ValueError("a one-channel %s band (post-proc codes IP-ERODED-3 / -11) needs guard >= %d rows at the resolution of the labelled map "
+                             "(2 * ksize + 1 with ksize %d: the reference leaves a crop unpadded within 2 * ksize = %d rows of an edge), got guard %d"
+                             % (tissue, 2 * k + 1, k, 2 * k, int(guard)))
         self.rank, self.world = rank, world
         self.band = band
         # the tissue's class map over the same rows (uint8, at the band's resolution), or None: its halo rows travel with the probability halos so
@@ -122,7 +205,11 @@ class BandState(object):
         self.top = 0 if from_above is None else int(from_above.shape[0])
         self.h_band = int(self.band.shape[0])
         self.h_win, self.w = int(window.shape[0]), int(window.shape[1])
-        self.lab, self.n = label_fn(window, self.tissue, self.ds)
+        # label_fn -> (labels, n) or (labels, n, n_suspect): n_suspect counts instances the labelling itself could not vouch for (bounded_label_fn: a
+        # window labelled in nested local bands reports its inner n_truncated + n_unresolved); it is added to this band's n_truncated
+        res = label_fn(window, self.tissue, self.ds)
+        self.lab, self.n = res[0], res[1]
+        inner_suspect = int(res[2]) if len(res) > 2 else 0
         if self.n > 0:
             tab = table_fn(self.lab, self.n)
             tab = tab.cpu().numpy() if torch.is_tensor(tab) else np.asarray(tab)
@@ -143,7 +230,7 @@ class BandState(object):
         if art_bot:
             cut |= y2 > self.h_win - self.guard
         self.cut = cut & alive
-        self.n_truncated = int((cut & self.in_band).sum())
+        self.n_truncated = int((cut & self.in_band).sum()) + inner_suspect
         # rank-local order of the owned instances = order of their first pixels
         own_idx = np.nonzero(self.owned)[0]
         self.own_sorted = own_idx[np.argsort(self.key[own_idx], kind="stable")]
@@ -337,8 +424,9 @@ def make_incremental(band_canv, dist, wsi_mode=True, margin=512, guard=48, max_b
             continue
         band = band_canv[key]
         mt = margin.get(t, margin.get("default", 512)) if isinstance(margin, dict) else margin
-        if local_band_count(int(band.shape[0]), int(band.shape[1]), max_band_px, mt) > 1:
-            pre[t] = IncrementalLocalLabeller(band, t, mt, guard, max_band_px)
+        mpx = eroded_max_band_px(max_band_px, t, band.shape[2], band.shape[1], mt)
+        if local_band_count(int(band.shape[0]), int(band.shape[1]), mpx, mt) > 1:
+            pre[t] = IncrementalLocalLabeller(band, t, mt, guard, mpx)
     return pre
 
 
@@ -537,7 +625,7 @@ def local_band_count(rows, cols, max_band_px, margin=0):
 
 
 def sharded_postprocess(canv, rank, world, dist, wsi_mode=True, margin=512, guard=48, max_band_px=None, prof=None, watch=None, pre=None, arrays=None,
-                        type_canv=None, fns=None):
+                        type_canv=None, fns=None, max_call_px=None):
     """Per-rank replacement of WSIRunner.postprocess for band canvases: label maps of THIS rank's band with slide-global
     ids, nothing gathered.  margin: halo rows at full resolution, an int or {tissue: rows, "default": rows} (the reference's
     own nuclei margin is 64 px, infer/wsi.py:906-915; gland clusters need hundreds).  canv: the band canvases of this rank (full-resolution rows of equal count on every rank except
@@ -550,7 +638,10 @@ def sharded_postprocess(canv, rank, world, dist, wsi_mode=True, margin=512, guar
     instead of the label maps (infer/wsi.py:805-853).  type_canv: the band's class canvases ("<Tissue>-TYPE", uint8, full resolution; default:
     the TYPE entries of `canv`) whose halo rows then travel with the probability halos.
     fns (multi-rank path): {"label", "table", "relabel", "arrays", "mask"} overriding the HIP kernels -- the gloo tests inject numpy stand-ins to
-    exercise the protocol (tests/test_host_logic.py); the product never passes it."""
+    exercise the protocol (tests/test_host_logic.py); the product never passes it.
+    max_call_px (multi-rank path): the pixel bound of one labelling call for a ONE-CHANNEL nuclei window (eroded scheme: the 2^31 crop-pixel limit of
+    cerb_postproc_eroded) -- a rank's window above eroded_max_band_px(max_call_px, ...) is labelled in nested local bands (bounded_label_fn).  The
+    one-rank path has max_band_px for that.  Two-channel windows are not touched by it."""
     fns = fns or {}
     f_label, f_table = fns.get("label", _device_label_fn), fns.get("table", _device_table_fn)
     f_relabel, f_arrays, f_mask = fns.get("relabel", _device_relabel_fn), fns.get("arrays", _device_arrays_fn), fns.get("mask", _device_mask_fn)
@@ -586,10 +677,12 @@ def sharded_postprocess(canv, rank, world, dist, wsi_mode=True, margin=512, guar
                 # the half-resolution tissues read the strided sub-sample of the class canvas (cerberus_amd.wsi.build_wsi_inst_info's stated deviation);
                 # band row offsets are even, so the band's sub-sample is the band's rows of the slide's sub-sample
                 tb = (tb[::2, ::2][: band.shape[0], : band.shape[1]] if half else tb[: band.shape[0], : band.shape[1]]).contiguous()
-            states[t] = dist_label(band, yy, t, m, g, dist, ds, f_label, f_table, prof=prof, watch=watch, type_band=tb)
+            fl = bounded_label_fn(f_label, max_call_px, m, g, f_table, f_relabel) if (max_call_px and t == "Nuclei" and band.shape[2] == 1) else f_label
+            states[t] = dist_label(band, yy, t, m, g, dist, ds, fl, f_table, prof=prof, watch=watch, type_band=tb)
         else:
             t0 = _tock(prof)
-            nb = local_band_count(int(band.shape[0]), int(band.shape[1]), max_band_px, m)  # (half-resolution maps: their own pixel count, halved margin)
+            # (half-resolution maps: their own pixel count, halved margin; one-channel nuclei maps: a quarter of the call size, ERODED_NUCLEI_CALL_SHARE)
+            nb = local_band_count(int(band.shape[0]), int(band.shape[1]), eroded_max_band_px(max_band_px, t, band.shape[2], band.shape[1], m), m)
             if pre and t in pre:  # bands already labelled underneath the inference (IncrementalLocalLabeller): finish the rest, same protocol
                 assert pre[t].nb == nb and pre[t].states[0].band.data_ptr() == band.data_ptr(), "the incremental labeller was built for another canvas"
                 outs, n, infos = pre[t].finish()
@@ -688,7 +781,7 @@ def _gather_rows(lab, rows_per_rank, cols, dist, rank, world):
 
 
 def postprocess_bands_and_gather(run, H, W, rank, world, dist, margin=512, guard=48, canv=None, max_band_px=None, prof=None, watch=None, pre=None,
-                                 parts=None, gather_maps=True):
+                                 parts=None, gather_maps=True, max_call_px=None):
     """The tail of a slide on 1..N GPUs: band-local label maps with slide-global ids, then only the int32 label bands and the
     uint8 / float class canvases travel to the root (12 + 3 B/px instead of the 36 B/px of raw probability canvases).
     `run` is this rank's WSIRunner after infer_band.  Returns (inst, info, small) -- inst / small are None off the root.
@@ -699,7 +792,8 @@ def postprocess_bands_and_gather(run, H, W, rank, world, dist, margin=512, guard
     window and the root receives the compact arrays -- `parts` is extended there with collect_wsi_inst_arrays' tuples, ready for the .dat
     writer (infer/wsi.py:805-853).  gather_maps=False: the label bands and the class canvases then stay where they are (`inst` is None, `small`
     holds only the quarter-resolution tissue map "Patch-Class@0.25" that tissue/<slide>.mat is written from): ~0.8 GB into the root
-    instead of 21 GB for a 40000^2 slide.  run_infer_wsi.py gathers the maps only under --save_label_maps."""
+    instead of 21 GB for a 40000^2 slide.  run_infer_wsi.py gathers the maps only under --save_label_maps.
+    max_call_px: see sharded_postprocess (one-channel nuclei windows of a rank, several ranks)."""
     from .wsi import gather_bands, half_size
 
     geo = run.geo
@@ -709,7 +803,7 @@ def postprocess_bands_and_gather(run, H, W, rank, world, dist, margin=512, guard
     local = OrderedDict() if (parts is not None and dist is not None) else None
     tcanv = OrderedDict((k, v[:valid, :W]) for k, v in run.canv.items() if k.endswith("TYPE"))
     inst_b, info = sharded_postprocess(band, rank, world, dist, wsi_mode=True, margin=margin, guard=guard, max_band_px=max_band_px, prof=prof, watch=watch, pre=pre,
-                                       arrays=local, type_canv=tcanv)
+                                       arrays=local, type_canv=tcanv, max_call_px=max_call_px)
     bounds = geo.bounds(world)
     rows = [max(0, min((bounds[i + 1] - bounds[i]) * geo.out, H - bounds[i] * geo.out)) for i in range(world)]
     from .launch import null_watch

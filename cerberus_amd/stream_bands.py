@@ -105,6 +105,11 @@ def plan_slide(net, slide_hw, win, out, batch, rank=0, world=1, want_twin=True, 
         return SlidePlan(mode="resident", sub_bands=1, twin=False, need=resident, budget=budget)
     why = "rank %d of %d: a %d x %d px band needs %.1f GB resident (%.1f canvases, the larger of %.1f slab and %.1f labels + labelling workspace, %.1f forward workspace) of %.1f GB" % (
         rank, world, band_rows, cw, resident / 1e9, px * cb_all / 1e9, phase_infer / 1e9, phase_label / 1e9, fwd / 1e9, budget / 1e9)
+    if allow_stream and any(hname == "INST" and int(och) == 2 for _, hname, och, _ in net._decoders):
+        # sub-band streaming walks (rows, W, 2) contour-scheme canvases (infer_and_label_streamed): a model with a two-class INST head (codes
+        # IP-ERODED-3 / -11, one canvas channel) is refused here, by name, before anything slide-sized exists
+        raise ValueError(why + "; a model with two-class INST heads (post-proc codes IP-ERODED-3 / IP-ERODED-11, --eroded_maps) is not streamed in "
+                         "sub-bands: use more ranks, or a device with room for the resident band")
     if not allow_stream:
         return SlidePlan(mode="resident", sub_bands=1, twin=False, need=resident, budget=budget, over_budget=why + "; streaming is not available on this path: trying resident")
     rows = r1 - r0

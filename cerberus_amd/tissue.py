@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .postproc import _workspace, get_inst_info_dict, inst_table_device, mask_lumen_by_gland, postproc_device
+from .postproc import _workspace, get_inst_info_dict, inst_table_device, mask_lumen_by_gland, postproc_device, postproc_eroded_device
 
 
 def load_mask(path):
@@ -95,19 +95,25 @@ def pclass_tissue_map(pclass, mask_dev=None):
 
 def half_inst_region(inst, region_lab=None, region_id=0):
     """x0.5 cv2-bilinear resize of an INST window (H, W, >=2) after keeping one region's mask pixels.  region_lab: CUDA int32
-    window of the mask's label map covering the same area (any resolution) or None."""
-    assert inst.is_cuda and inst.dtype == torch.float32 and inst.dim() == 3 and inst.stride(2) == 1
+    window of the mask's label map covering the same area (any resolution) or None.  A one-channel window (H, W, 1) -- the map of a two-class
+    INST head -- gives (H/2, W/2, 1) through cerb_downsample2_map_region."""
+    assert inst.is_cuda and inst.dtype == torch.float32 and inst.dim() == 3 and (inst.stride(2) == 1 or inst.shape[2] == 1)
     L = _lib.lib()
     h, w = int(inst.shape[0]), int(inst.shape[1])
-    out = torch.empty((L.cerb_half_size(h), L.cerb_half_size(w), 2), dtype=torch.float32, device=inst.device)
+    nch = 1 if int(inst.shape[2]) == 1 else 2
+    out = torch.empty((L.cerb_half_size(h), L.cerb_half_size(w), nch), dtype=torch.float32, device=inst.device)
     lp, ls, mh, mw = None, 0, 0, 0
     if region_lab is not None:
         assert region_lab.is_cuda and region_lab.dtype == torch.int32 and region_lab.stride(1) == 1
         lp, ls, mh, mw = region_lab.data_ptr(), region_lab.stride(0), int(region_lab.shape[0]), int(region_lab.shape[1])
     st = torch.cuda.current_stream(inst.device).cuda_stream
     with torch.cuda.device(inst.device):
-        _lib.check(L.cerb_downsample2_inst_region(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, lp, ls, mh, mw, int(region_id), out.data_ptr(),
-                                                  C.c_void_p(st)))
+        if nch == 1:
+            _lib.check(L.cerb_downsample2_map_region(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, 1, lp, ls, mh, mw, int(region_id), out.data_ptr(),
+                                                     C.c_void_p(st)))
+        else:
+            _lib.check(L.cerb_downsample2_inst_region(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, lp, ls, mh, mw, int(region_id), out.data_ptr(),
+                                                      C.c_void_p(st)))
     return out
 
 
@@ -136,7 +142,8 @@ def postprocess_regions(canv, slide_hw, regions=None, with_info=True):
             if crop.shape[0] < 1 or crop.shape[1] < 1:
                 continue
             half = half_inst_region(crop, win, rid if rid is not None else 0)
-            inst[t], _ = postproc_device(half, t, 0.5)
+            # one channel: PostProcInstErodedMap on the masked, halved crop -- full-resolution parameters, its `scale` is never read (infer/wsi.py:792-794)
+            inst[t], _ = postproc_eroded_device(half, t) if half.shape[2] == 1 else postproc_device(half, t, 0.5)
             tm = canv.get(t + "-TYPE")
             if tm is not None and with_info:
                 sub = tm[rmin:rmax, cmin:cmax][::2, ::2][: half.shape[0], : half.shape[1]].contiguous()

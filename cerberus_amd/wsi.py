@@ -27,7 +27,7 @@ import torch
 from .inst_info import _uuid4_hex, write_dat  # noqa: F401
 
 from . import _lib
-from .postproc import mask_lumen_by_gland, postproc_device
+from .postproc import mask_lumen_by_gland, postproc_device, postproc_eroded_device
 
 
 def band_partition(n_rows, world_size):
@@ -126,11 +126,17 @@ def half_size(n):
 
 
 def downsample2_inst(inst):
+    """x0.5 resize of an INST canvas: (h, w, >= 2) -> (h/2, w/2, 2) as ever; the one-channel canvas of a two-class INST head (h, w, 1) ->
+    (h/2, w/2, 1) through cerb_downsample2_map, which reads and writes that one channel only."""
     h, w = int(inst.shape[0]), int(inst.shape[1])
-    out = torch.empty((half_size(h), half_size(w), 2), dtype=torch.float32, device=inst.device)
+    nch = 1 if (inst.dim() == 3 and int(inst.shape[2]) == 1) else 2
+    out = torch.empty((half_size(h), half_size(w), nch), dtype=torch.float32, device=inst.device)
     st = torch.cuda.current_stream(inst.device).cuda_stream
     with torch.cuda.device(inst.device):
-        _lib.check(_lib.lib().cerb_downsample2_inst(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, out.data_ptr(), C.c_void_p(st)))
+        if nch == 1:
+            _lib.check(_lib.lib().cerb_downsample2_map(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, 1, out.data_ptr(), C.c_void_p(st)))
+        else:
+            _lib.check(_lib.lib().cerb_downsample2_inst(inst.data_ptr(), inst.stride(0), inst.stride(1), h, w, out.data_ptr(), C.c_void_p(st)))
     return out
 
 
@@ -163,7 +169,7 @@ def check_shardable(slide_hw, patch_output_shape, world_size):
         raise ValueError("slide of %d patch rows cannot be sharded over %d ranks: use at most %d" % (rows, world_size, rows))
 
 
-ERODED_CODES = ("IP-ERODED-3", "IP-ERODED-11")  # PostProcInstErodedMap (infer/wsi.py:51-56): tile mode only here (cerberus_amd/tile.py)
+ERODED_CODES = ("IP-ERODED-3", "IP-ERODED-11")  # PostProcInstErodedMap (infer/wsi.py:51-56): refused on slides unless asked for (eroded_maps=True)
 
 
 def refuse_eroded_codes(decoder_dict=None, net=None):
@@ -180,14 +186,33 @@ def refuse_eroded_codes(decoder_dict=None, net=None):
                                       "only (run_infer_tile.py); the slide driver implements IP-ERODED-CONTOUR-3 / -11" % key)
 
 
+def eroded_heads(net):
+    """Keys of the two-class INST heads of a NetDesc (codes IP-ERODED-3 / -11: ONE canvas channel)."""
+    return [key for _, hname, och, key in net._decoders if hname == "INST" and int(och) == 2]
+
+
+def check_eroded_slide_options(net=None, decoder_dict=None, reference_tiling=False):
+    """What the opt-in slide path for IP-ERODED-3 / -11 models (eroded_maps=True, run_infer_wsi.py --eroded_maps) still refuses, by name and before
+    anything is allocated: --reference_tiling with a one-channel Nuclei head -- the reference's tile / margin / strip scheme (cerberus_amd/ref_tiling.py)
+    is written for the contour scheme's watershed.  (Sub-band streaming is refused in cerberus_amd.stream_bands.plan_slide.)"""
+    nuc = "Nuclei-INST" in (eroded_heads(net) if net is not None else []) or (decoder_dict or {}).get("Nuclei-INST") in ERODED_CODES
+    if reference_tiling and nuc:
+        raise ValueError("--reference_tiling with Nuclei-INST code IP-ERODED-3 / IP-ERODED-11 (a two-class, one-channel head): the reference's "
+                         "nuclei tile scheme is implemented for IP-ERODED-CONTOUR-3 only; run --eroded_maps without --reference_tiling")
+
+
 class WSIRunner(object):
     """One per process / GPU.  (Single-process simulations of more ranks than patch rows get empty bands; distributed drivers call
     check_shardable first.)"""
 
-    def __init__(self, net, slide_hw, patch_input_shape=256, patch_output_shape=256, batch_size=32, rank=0, world_size=1, patch_sel=None, twin=None, row_range=None):
+    def __init__(self, net, slide_hw, patch_input_shape=256, patch_output_shape=256, batch_size=32, rank=0, world_size=1, patch_sel=None, twin=None, row_range=None,
+                 eroded_maps=False):
         """twin: a second handle with the same parameters (NetDesc.twin()); batches then alternate between the two on two side streams.
-        row_range: (r0, r1) patch rows instead of rank's band of the world -- the sub-bands of cerberus_amd.stream_bands (slides larger than HBM)."""
-        refuse_eroded_codes(net=net)  # before any canvas is allocated
+        row_range: (r0, r1) patch rows instead of rank's band of the world -- the sub-bands of cerberus_amd.stream_bands (slides larger than HBM).
+        eroded_maps: False refuses a model with a two-class INST head (codes IP-ERODED-3 / -11) by name; True gives such a head a (band_h, canvas_w, 1)
+        canvas -- the layout net._run writes for it in the tile driver -- and the labelling dispatches on the channel count per tissue."""
+        if not eroded_maps:
+            refuse_eroded_codes(net=net)  # before any canvas is allocated
         self.net = net
         self.twin = twin
         self._side = None
@@ -203,7 +228,7 @@ class WSIRunner(object):
         self.canv = OrderedDict()
         for name, hname, och, key in net._decoders:
             if hname == "INST":
-                self.canv[key] = torch.zeros((self.band_h, self.canvas_w, 2), dtype=torch.float32, device=self.dev)
+                self.canv[key] = torch.zeros((self.band_h, self.canvas_w, int(och) - 1), dtype=torch.float32, device=self.dev)  # (2; 1 under eroded_maps)
             elif hname == "TYPE":
                 self.canv[key] = torch.zeros((self.band_h, self.canvas_w), dtype=torch.uint8, device=self.dev)
             else:
@@ -382,10 +407,12 @@ class WSIRunner(object):
     @staticmethod
     def postprocess(canv, wsi_mode=True):
         """Label maps from stitched canvases (rank 0).  wsi_mode: gland / lumen at x0.5 with ds_factor 0.5
-        (infer/wsi.py:786-804); otherwise tile-mode semantics at full resolution (infer/tile.py:168-191)."""
+        (infer/wsi.py:786-804); otherwise tile-mode semantics at full resolution (infer/tile.py:168-191).  The scheme is chosen per tissue by the
+        canvas's channel count: two channels = the contour scheme, one = PostProcInstErodedMap, which takes no ds_factor (infer/wsi.py:792-794 hands it
+        one, loader/postproc.py:245-257 never reads it: the half-resolution maps are labelled with the full-resolution parameters)."""
         inst, info = OrderedDict(), OrderedDict()
         if "Nuclei-INST" in canv:
-            inst["Nuclei"], info["Nuclei"] = postproc_device(canv["Nuclei-INST"], "Nuclei", exact_ties=False)
+            inst["Nuclei"], info["Nuclei"] = label_inst_map(canv["Nuclei-INST"], "Nuclei", exact_ties=False)
         for t in ("Gland", "Lumen"):
             key = t + "-INST"
             if key not in canv:
@@ -393,12 +420,20 @@ class WSIRunner(object):
             if wsi_mode:
                 from .tissue import half_inst_region
 
-                inst[t], info[t] = postproc_device(half_inst_region(canv[key]), t, 0.5)
+                inst[t], info[t] = label_inst_map(half_inst_region(canv[key]), t, 0.5)
             else:
-                inst[t], info[t] = postproc_device(canv[key], t, 1.0)
+                inst[t], info[t] = label_inst_map(canv[key], t, 1.0)
         if "Lumen" in inst and "Gland" in inst:
             mask_lumen_by_gland(inst["Lumen"], inst["Gland"])
         return inst, info
+
+
+def label_inst_map(m, tissue, ds_factor=1.0, exact_ties=True):
+    """One INST map -> (int32 label map, info), the scheme chosen by the map's channel count: (H, W, 1) -> postproc_eroded_device (no ds_factor: the
+    reference's eroded class ignores it), (H, W, >= 2) -> postproc_device as before."""
+    if m.dim() == 3 and int(m.shape[2]) == 1:
+        return postproc_eroded_device(m, tissue)
+    return postproc_device(m, tissue, ds_factor, exact_ties=exact_ties)
 
 
 def build_wsi_inst_info(inst, canv, slide_hw, proc_mag, ds_factor=0.5, region_records=None, base_mag=None, base_hw=None, prebuilt=None):

@@ -211,6 +211,10 @@ int cerb_resample_area(const uint8_t* src, long long src_row_stride, int src_row
  *                       (infer/wsi.py:742-776): region_lab = int32 label map of the mask (cerb_label_mask) cropped to the
  *                       region's bounding box [mh][mw], resized to [h][w] like cv2.resize(INTER_NEAREST); samples whose
  *                       mask label != region_id count as 0.  region_lab NULL = no mask.
+ * cerb_downsample2_map / cerb_downsample2_map_region: the same two calls with the channel count as an argument: n_ch = 2 is
+ *                       the call above, n_ch = 1 reads ONE float per source pixel (the map of a two-class INST head, codes
+ *                       IP-ERODED-3 / -11) and writes dst[..][..][1]; plane c of an n_ch-channel call is bit-equal to plane c
+ *                       of the two-channel call on the same data.  pix_stride >= n_ch.
  * cerb_pclass_tissue_map: dst[cvRound(h/4)][cvRound(w/4)] = cv2.resize(pclass, fx=fy=0.25, INTER_NEAREST) times the
  *                       INTER_NEAREST-resized slide mask (infer/wsi.py:688-716); mask NULL = all tissue.
  * cerb_label_mask     : 4-connected components of mask != 0, ids in raster order of first pixel (scipy.ndimage.label,
@@ -224,6 +228,11 @@ int cerb_half_size(int n);
 int cerb_downsample2_inst_region(const float* src, long long row_stride, int pix_stride, int h, int w,
                                  const int32_t* region_lab, long long lab_row_stride, int mh, int mw, int region_id,
                                  float* dst, void* hip_stream);
+int cerb_downsample2_map(const float* src, long long row_stride, int pix_stride, int h, int w, int n_ch, float* dst,
+                         void* hip_stream);
+int cerb_downsample2_map_region(const float* src, long long row_stride, int pix_stride, int h, int w, int n_ch,
+                                const int32_t* region_lab, long long lab_row_stride, int mh, int mw, int region_id,
+                                float* dst, void* hip_stream);
 int cerb_pclass_tissue_map(const float* pclass, long long row_stride, int h, int w, const uint8_t* mask,
                            long long mask_row_stride, int mh, int mw, float* dst, void* hip_stream);
 int cerb_label_mask(const uint8_t* mask, long long row_stride, int h, int w, int32_t* labels_out, int32_t* n_out,

@@ -8,6 +8,8 @@ parses and then overrides with constants are accepted and ignored.  `--msk_dir` 
 tissue do not run, the Patch-Class map is masked, gland / lumen are labelled per tissue region (cerberus_amd/tissue.py); every
 slide also gets `tissue/<slide>.mat` (infer/wsi.py:688-716).  `--auto_mask` makes that mask on the device instead, from a thumbnail of the slide at
 1/`--auto_mask_ds` of the processing resolution (the reference's get_tissue_mask, misc/utils.py:195-244); everything after it is the `--msk_dir` path.
+A model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, one canvas channel, PostProcInstErodedMap) is refused by name unless
+`--eroded_maps` is given; with it such heads get one-channel canvases and are labelled through the same bands (not with `--reference_tiling` for nuclei).
 
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N run_infer_wsi.py ...`; patch rows shard into one
 contiguous band per rank, inference needs no collective, post-processing is band-local (cerberus_amd/shard_postproc.py)."""
@@ -20,7 +22,7 @@ import time
 
 import numpy as np
 
-from cerberus_amd.cli import WSI_OPTIONS, parse, require_model
+from cerberus_amd.cli import WSI_ALL_OPTIONS, parse, require_model
 
 
 # largest map labelled in one call on one GPU (400 Mpx = 38 GB of workspace); larger slides are labelled in row bands (CERB_ONE_CALL_MPX moves the line)
@@ -114,7 +116,7 @@ def _check_auto_mask(args):
 
 
 def main(argv=None):
-    args = parse("run_infer_wsi.py", WSI_OPTIONS, argv, version="CoBi Gland Inference")
+    args = parse("run_infer_wsi.py", WSI_ALL_OPTIONS, argv, version="CoBi Gland Inference")
     require_model(args)
     _check_auto_mask(args)
     if args["--jpeg_decode"] not in ("host", "device"):
@@ -138,7 +140,7 @@ def main(argv=None):
 
     from cerberus_amd.tile import InferManager
     from cerberus_amd.weights import DEFAULT_REQ_TARGET_CODE, default_model_kwargs
-    from cerberus_amd.wsi import DatWriter, SlabUploader, WSIRunner, check_shardable, collect_wsi_inst_arrays, refuse_eroded_codes, synth_slide, wsi_meta
+    from cerberus_amd.wsi import DatWriter, SlabUploader, WSIRunner, check_shardable, check_eroded_slide_options, collect_wsi_inst_arrays, eroded_heads, label_inst_map, refuse_eroded_codes, synth_slide, wsi_meta
 
     dist, watch = None, launch.null_watch()
     n_dev = max(1, torch.cuda.device_count())
@@ -167,12 +169,18 @@ def main(argv=None):
         with open(os.path.join(args["--model"], "settings.yml")) as fh:
             settings = yaml.full_load(fh)
         decoders, model_args = settings["dataset_kwargs"]["req_target_code"], settings["model_kwargs"]
-    refuse_eroded_codes(decoders)  # IP-ERODED-3 / -11 models: tile mode only -- said by name before the model is loaded or a canvas allocated
+    eroded_maps = bool(args["--eroded_maps"])
+    if not eroded_maps:
+        refuse_eroded_codes(decoders)  # IP-ERODED-3 / -11 models: tile mode only -- said by name before the model is loaded or a canvas allocated
+    else:  # opted in: one-channel canvases for the two-class INST heads; what that path cannot do yet is said by name here, before anything is loaded
+        check_eroded_slide_options(decoder_dict=decoders, reference_tiling=bool(args["--reference_tiling"]))
     if (args["--wsi_file_ext"] or "").lower() in (".tif", ".tiff", ".svs"):  # tiled files: their tile-decode worker processes start underneath the model's loading
         from cerberus_amd.reader import warm_decode_workers
 
         warm_decode_workers()
     manager = InferManager(checkpoint_path=checkpoint, decoder_dict=decoders, model_args=model_args)
+    if eroded_maps:  # (a two-class head is such a head whatever settings.yml says)
+        check_eroded_slide_options(net=manager.net, reference_tiling=bool(args["--reference_tiling"]))
     # a second handle with the same weights (WSIRunner alternates batches between the two on two streams: +2 .. 3 %; CERB_WSI_STREAMS=1: one handle)
     # is made per slide, and only when cerberus_amd.stream_bands.plan_slide finds room for its workspace beside everything else
     want_twin = os.environ.get("CERB_WSI_STREAMS", "2") == "2"
@@ -251,6 +259,21 @@ def main(argv=None):
 
         plan = plan_slide(manager.net, (H, W), win, out, batch, rank, world, want_twin=want_twin, max_band_px=ONE_CALL_PX if world == 1 else None,
                           allow_stream=(mask is None and not args["--reference_tiling"]))
+        # The largest nuclei map labelled in ONE call: ONE_CALL_PX -- or, for the one-channel map of a two-class Nuclei head (--eroded_maps), the lower
+        # bound that keeps a call's instance crops clear of cerb_postproc_eroded's 2^31-pixel limit (shard_postproc.eroded_max_band_px).  Every
+        # path below labels such a map in row bands above it: this rank's band is checked for that NOW, before anything slide-sized exists.
+        one_call_px, nuclei_call_px = ONE_CALL_PX, None
+        if eroded_maps and "Nuclei-INST" in eroded_heads(manager.net):
+            from cerberus_amd.shard_postproc import check_eroded_nuclei_calls, eroded_max_band_px
+            from cerberus_amd.wsi import SlideGeometry as _Geo
+
+            nuclei_call_px = ONE_CALL_PX
+            one_call_px = eroded_max_band_px(ONE_CALL_PX, "Nuclei", 1, W, 512)
+            if mask is not None:  # (with a tissue mask the canvases are gathered and the root labels the whole slide's nuclei map)
+                check_eroded_nuclei_calls(H, W, ONE_CALL_PX, 512, 1)
+            else:
+                r0_, r1_ = _Geo((H, W), win, out, sel).band(rank, world)
+                check_eroded_nuclei_calls(max(0, min((r1_ - r0_) * out, H - r0_ * out)), W, ONE_CALL_PX, 512, world)
         if dist is not None:  # the streamed and the resident tail use different collectives: one mode for all ranks
             with watch.phase("memory-plan agreement (%s)" % base):
                 plan = agree_on_plan(plan, dist, torch.device("cuda", local) if backend == "nccl" else "cpu")
@@ -297,7 +320,7 @@ def main(argv=None):
                 log.info("Inference Time: {0} ({1} sub-bands streamed through HBM)".format(pprof.get("stream_infer_s"), plan.sub_bands))
                 log.info("Nuclei, Gland & Lumen Labelling Time (inside the stream): {0}".format(pprof.get("stream_label_s")))
         else:
-            run = WSIRunner(manager.net, (H, W), win, out, batch, rank, world, patch_sel=sel, twin=twin if plan.twin else None)
+            run = WSIRunner(manager.net, (H, W), win, out, batch, rank, world, patch_sel=sel, twin=twin if plan.twin else None, eroded_maps=eroded_maps)
             y0, y1 = run.slab_rows()  # this rank's band + context halo
             t_prep = time.perf_counter()
             if log:
@@ -353,7 +376,7 @@ def main(argv=None):
             records = None
             pprof = {}
             rank_parts = None
-            if mask is None and (dist is not None or H * W > ONE_CALL_PX):
+            if mask is None and (dist is not None or H * W > one_call_px):
                 # band-local labelling with slide-global ids; only int32 label bands and the class maps travel to the root.  On ONE GPU a
                 # slide too large for a single labelling call (96 B / px of workspace, 2^31 px) streams through the same protocol band by band
                 from cerberus_amd.shard_postproc import postprocess_bands_and_gather
@@ -362,18 +385,19 @@ def main(argv=None):
                 # receives those compact arrays (~0.4 GB for a 40000^2 slide) plus the quarter-resolution tissue map; the int32 label bands and the
                 # class canvases (15 B / px = 21 GB) only travel when the maps themselves are asked for (--save_label_maps)
                 rank_parts = [] if (dist is not None and not args["--save_label_maps"]) else None
-                inst, _, maps = postprocess_bands_and_gather(run, H, W, rank, world, dist, max_band_px=ONE_CALL_PX if world == 1 else None, prof=pprof, watch=watch, pre=pre,
-                                                             parts=rank_parts, gather_maps=rank_parts is None)
+                inst, binfo, maps = postprocess_bands_and_gather(run, H, W, rank, world, dist, max_band_px=ONE_CALL_PX if world == 1 else None, prof=pprof, watch=watch, pre=pre,
+                                                                 parts=rank_parts, gather_maps=rank_parts is None, max_call_px=nuclei_call_px)
+                if log and nuclei_call_px:
+                    log.info("Nuclei (one channel) labelled in calls of at most {0} pixels: {1}".format(one_call_px, binfo.get("Nuclei")))
             else:  # with a mask gland / lumen are labelled per tissue region (infer/wsi.py:730-835), on the root
                 with watch.phase("canvas gather to rank 0 (%s)" % base):
                     maps = run.gather_to_root(dist)
                 if rank == 0 and mask is not None:
-                    from cerberus_amd.postproc import postproc_device
                     from cerberus_amd.tissue import postprocess_regions
 
                     regions = TissueRegions(torch.from_numpy(mask).cuda())
                     inst = {}
-                    if "Nuclei-INST" in maps and H * W > ONE_CALL_PX:
+                    if "Nuclei-INST" in maps and H * W > one_call_px:
                         # (nuclei do not care about tissue regions -- unselected patches left zeros -- so a slide too large for one labelling call, or past
                         #  2^31 pixels, goes through the row bands of the mask-less path: exact ownership, slide-global ids)
                         from cerberus_amd.shard_postproc import sharded_postprocess
@@ -384,7 +408,7 @@ def main(argv=None):
                             bad = ninfo["Nuclei"].get("n_truncated") or ninfo["Nuclei"].get("n_unresolved")
                             (log.warning if bad else log.info)("Nuclei labelled in {0} row bands under the tissue mask: {1}".format(ninfo["Nuclei"].get("local_bands"), ninfo["Nuclei"]))
                     elif "Nuclei-INST" in maps:
-                        inst["Nuclei"] = postproc_device(maps["Nuclei-INST"], "Nuclei", exact_ties=False)[0]
+                        inst["Nuclei"] = label_inst_map(maps["Nuclei-INST"], "Nuclei", exact_ties=False)[0]
                     records = postprocess_regions(maps, (H, W), regions)
                 elif rank == 0:
                     inst, _ = WSIRunner.postprocess(maps, wsi_mode=True)
