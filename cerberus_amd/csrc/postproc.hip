@@ -51,15 +51,13 @@ static inline unsigned nblk(long long n, int per) { return (unsigned)((n + per -
 // Exclusive prefix sum over int32 (three-kernel, recursive on the block sums)
 // =================================================================================================================
 #define SCAN_ITEMS 1024  // per block: 256 threads x 4
-// ROOTS: the scanned value is "pixel j is a root of the union-find map `in`" (in[j] == j), computed here instead of by a flag pass of its own
-template <bool ROOTS>
 __global__ __launch_bounds__(256) void scan_block_kernel(const int* __restrict__ in, int* __restrict__ out, int* __restrict__ sums, int n) {
     __shared__ int wsum[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long base = (long long)blockIdx.x * SCAN_ITEMS + tid * 4;
     int v[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (base + i < n) ? (ROOTS ? (in[base + i] == (int)(base + i) ? 1 : 0) : in[base + i]) : 0;
+    for (int i = 0; i < 4; ++i) v[i] = (base + i < n) ? in[base + i] : 0;
     const int tsum = v[0] + v[1] + v[2] + v[3];
     int inc = tsum;  // inclusive scan across the wave
 #pragma unroll
@@ -88,25 +86,17 @@ __global__ void scan_add_kernel(int* __restrict__ out, const int* __restrict__ s
         if (j < n) out[j] += add;
     }
 }
-// tmp must hold at least n/1024 + n/1024^2 + ... + 4 ints.  total (sum of all elements) is written to *total_dev.
-// block_offsets != nullptr: the last pass (adding every block's offset to its 1024 outputs: a read-modify-write of the whole array) is left to
-// the READERS -- scan[j] = out[j] + (*block_offsets)[j >> 10], with *block_offsets == nullptr when one block held everything.
-static int scan_exclusive(const int* in, int* out, int n, int* tmp, hipStream_t st, bool roots = false, const int** block_offsets = nullptr) {
+// tmp must hold at least n/1024 + n/1024^2 + ... + 4 ints.
+static int scan_exclusive(const int* in, int* out, int n, int* tmp, hipStream_t st) {
     const int nb = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
-    auto kern = roots ? scan_block_kernel<true> : scan_block_kernel<false>;
-    if (block_offsets) *block_offsets = nullptr;
     if (nb <= 1) {
-        hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, st, in, out, (int*)nullptr, n);
+        hipLaunchKernelGGL(scan_block_kernel, dim3(1), dim3(256), 0, st, in, out, (int*)nullptr, n);
         KCHECK();
         return 0;
     }
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, in, out, tmp, n);
+    hipLaunchKernelGGL(scan_block_kernel, dim3(nb), dim3(256), 0, st, in, out, tmp, n);
     KCHECK();
     if (scan_exclusive(tmp, tmp, nb, tmp + ((nb + 3) & ~3), st)) return 1;
-    if (block_offsets) {
-        *block_offsets = tmp;
-        return 0;
-    }
     hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(256), 0, st, out, tmp, n);
     KCHECK();
     return 0;
@@ -201,51 +191,6 @@ __device__ __forceinline__ void uf_union(int* L, int a, int b) {
     } while (!done);
 }
 
-// fg: foreground predicate bytes compared against `val` (lets one byte plane serve a mask and its complement).
-// Run-based initialisation: a wave owns 64 consecutive pixels; every pixel is linked straight to the first pixel of its
-// horizontal run inside that 64-pixel chunk (ballot + count-leading-zeros, no atomics), so the merge pass only needs one
-// union per run and row pair instead of two per pixel.
-__global__ void ccl_init_kernel(const uint8_t* __restrict__ fg, uint8_t val, int* __restrict__ L, int n, int W) {
-    const int lane = threadIdx.x & 63;
-    const double invW = 1.0 / (double)W;
-    for (long long p0 = (blockIdx.x * (long long)blockDim.x + threadIdx.x) - lane; p0 < n; p0 += (long long)gridDim.x * blockDim.x) {
-        const long long p = p0 + lane;
-        const bool f = p < n && fg[p] == val;
-        int y_, x_;
-        pix_yx(p < n ? p : 0, W, invW, y_, x_);
-        const bool link = f && lane > 0 && x_ != 0 && fg[p - 1] == val;  // joined to the previous lane's pixel
-        const u64 starts = __ballot(f && !link);
-        if (f) {
-            const u64 below = starts & ((2ull << lane) - 1);  // run starts at or below this lane
-            L[p] = (int)(p0 + 63 - __clzll((long long)below));
-        } else if (p < n)
-            L[p] = -1;
-    }
-}
-__global__ void ccl_merge_kernel(const uint8_t* __restrict__ fg, uint8_t val, int* L, int H, int W) {
-    const long long n = (long long)H * W;
-    const double invW = 1.0 / (double)W;
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
-        if (fg[p] != val) continue;
-        int y_, x;
-        pix_yx(p, W, invW, y_, x);
-        const bool left = x > 0 && fg[p - 1] == val;
-        const bool chunk_start = (p & 63) == 0 || !left;  // first pixel of its run inside the 64-pixel chunk
-#ifndef PP_ABL_NOUNION
-        if (left && (p & 63) == 0) uf_union(L, (int)p, (int)p - 1);  // run continues across the chunk boundary
-#endif
-        if (p >= W && fg[p - W] == val) {
-            // one union per (upper run, lower run) pair: at the first column where they overlap either the lower run starts
-            // here, or the upper run does (its left neighbour is background)
-            const bool up_starts = !(x > 0 && fg[p - W - 1] == val);
-#ifndef PP_ABL_NOUNION
-            if (chunk_start || up_starts) uf_union(L, (int)p, (int)(p - W));
-#else
-            if ((chunk_start || up_starts) && L[p] == -12345) L[p] = 0;
-#endif
-        }
-    }
-}
 __global__ void ccl_flatten_kernel(int* L, int n) {
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
         if (L[p] < 0) continue;
@@ -253,7 +198,7 @@ __global__ void ccl_flatten_kernel(int* L, int n) {
     }
 }
 // flatten + component areas in one pass over L: area[root] += the length of each RUN of equal roots inside the wave (64 consecutive pixels of a
-// row hold a few runs; the separate ccl_area_kernel pass re-read all of L for the same atomics).  `area` is zeroed by the caller.
+// row hold a few runs; a separate area pass would re-read all of L for the same atomics).  `area` is zeroed by the caller.
 __global__ void ccl_flatten_area_kernel(int* L, int* __restrict__ area, int n) {
     const int lane = threadIdx.x & 63;
     for (long long base = (blockIdx.x * (long long)blockDim.x + threadIdx.x) - lane; base < n; base += (long long)gridDim.x * blockDim.x) {
@@ -281,7 +226,7 @@ static unsigned grid_for(long long n) {
 // Tile-local labelling (round 2): a workgroup labels a 64 x 32-pixel tile with its union-find in LDS (an LDS atomic is ~20x cheaper than
 // the L2 round trips of a global uf_union, and a run-pair union of the global merge pass cost 2-3 us of serial latency), writes every
 // pixel's tile root as a GLOBAL index, and only the pixel pairs across tile borders (1/32 of the rows, 1/64 of the columns) go through
-// the global union-find.  Roots stay "smallest raster index of the component", so the labels are the ones ccl_init / ccl_merge gave.
+// the global union-find.  Roots stay "smallest raster index of the component".
 constexpr int CT_W = 64, CT_H = 32;
 // first slot of a tile's range in the root list: the pixels of the tile rows above it + of the tiles to its left in its own tile row
 // (a tile gets as many slots as it has pixels, the list as many as the map)
@@ -475,17 +420,12 @@ __global__ void ccl_seam_kernel(const uint8_t* __restrict__ fg, uint8_t val, int
 }
 static int ccl_run(const uint8_t* fg, uint8_t val, int* L, int H, int W, hipStream_t st, int* area = nullptr) {
     const int n = H * W;
-#ifdef PP_CCL_GLOBAL  // round 1's labelling: run-based init + one global union per run pair
-    hipLaunchKernelGGL(ccl_init_kernel, dim3(grid_for(n)), dim3(256), 0, st, fg, val, L, n, W);
-    hipLaunchKernelGGL(ccl_merge_kernel, dim3(grid_for(n)), dim3(256), 0, st, fg, val, L, H, W);
-#else
     const int tiles_x = (W + CT_W - 1) / CT_W, tiles_y = (H + CT_H - 1) / CT_H;
     const int n_tiles = tiles_x * tiles_y;
     hipLaunchKernelGGL(ccl_tile_kernel<false>, dim3(n_tiles < 256 * 16 ? n_tiles : 256 * 16), dim3(256), 0, st, fg, val, L, H, W, tiles_x, n_tiles, (int*)nullptr,
                        (int*)nullptr, (int*)nullptr);
     const long long seams = (long long)(tiles_x - 1) * H + (long long)(tiles_y - 1) * W;
     if (seams > 0) hipLaunchKernelGGL(ccl_seam_kernel, dim3(grid_for(seams)), dim3(256), 0, st, fg, val, L, H, W, tiles_x, tiles_y);
-#endif
     if (area) hipLaunchKernelGGL(ccl_flatten_area_kernel, dim3(grid_for(n)), dim3(256), 0, st, L, area, n);
     else hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(n)), dim3(256), 0, st, L, n);
     KCHECK();
@@ -506,7 +446,7 @@ static int ccl_run(const uint8_t* fg, uint8_t val, int* L, int H, int W, hipStre
 // roots under roots, so the nodes of the forest above the pixel level are exactly these: flattening the LIST (ccl2_flatten_roots_kernel) makes
 // L[L[p]] the set's root for every pixel p -- two loads, no pointer chase, no pass that walks 67 M background pixels up to one giant root.
 __global__ __launch_bounds__(256) void ccl2_tile_kernel(const uint8_t* __restrict__ fg, int* __restrict__ L, int H, int W, int tiles_x, int n_tiles,
-                                                        int* __restrict__ roots, int* __restrict__ cnt, int* __restrict__ area, int* __restrict__ colbuf = nullptr) {
+                                                        int* __restrict__ roots, int* __restrict__ cnt, int* __restrict__ area, int* __restrict__ colbuf) {
     __shared__ int swtot[4];
     __shared__ int sl[CT_H * CT_W];
     __shared__ int scnt[CT_H * CT_W];  // FOREGROUND pixels of every tile-local set (background sets stay at 0: ccl2_drop_small_kernel relies on it)
@@ -551,11 +491,10 @@ __global__ __launch_bounds__(256) void ccl2_tile_kernel(const uint8_t* __restric
                 L[(long long)y * W + x] = g;
                 is_root = root == r * CT_W + lane;
                 const u64 c = sc[r];
-                if (colbuf) {  // border columns for the seam pass (see ccl_seam_kernel): the tile root, the pixel's colour in bit 31 (indices stay below 2^31)
-                    const int gc = g | (int)(((c >> lane) & 1ull) << 31);
-                    if (lane == 0 && tx0 > 0) colbuf[(long long)(tx0 / CT_W - 1) * H + y] = gc;
-                    if (lane == CT_W - 1 && tx0 + CT_W < W) colbuf[(long long)(tiles_x - 1) * H + (long long)(tx0 / CT_W) * H + y] = gc;
-                }
+                // border columns for the seam pass (see ccl_seam_kernel): the tile root, the pixel's colour in bit 31 (indices stay below 2^31)
+                const int gc = g | (int)(((c >> lane) & 1ull) << 31);
+                if (lane == 0 && tx0 > 0) colbuf[(long long)(tx0 / CT_W - 1) * H + y] = gc;
+                if (lane == CT_W - 1 && tx0 + CT_W < W) colbuf[(long long)(tiles_x - 1) * H + (long long)(tx0 / CT_W) * H + y] = gc;
                 if (((c & ss[r]) >> lane) & 1ull) {  // first pixel of a foreground run: its length (the colour bits beyond the image are 0)
                     const u64 rest = ~(c >> lane);
                     atomicAdd(&scnt[root], rest ? __ffsll((long long)rest) - 1 : 64 - lane);
@@ -603,7 +542,7 @@ __global__ void ccl2_flatten_roots_kernel(int* L, const int* __restrict__ roots,
         }
     }
 }
-// Seam unions with CACHED finds (0.27 -> 0.17 ms for the marker image's seams at 8192^2; CERB_PP_SEAM_STRICT=1 keeps uf_union): uf_find's agent-scope
+// Seam unions with CACHED finds (0.27 -> 0.17 ms for the marker image's seams at 8192^2 against uf_union): uf_find's agent-scope
 // loads go past the L2 on every step; a plain load may be
 // stale, but a stale parent is still an ancestor (links only ever move towards smaller indices inside one set) and the returning atomicMin that
 // closes a union validates the root it acts on -- a root that was no root any more hands back its real parent and the loop continues from there.
@@ -635,8 +574,7 @@ __device__ __forceinline__ void uf_union_relaxed(int* L, int a, int b) {
             done = true;
     } while (!done);
 }
-template <bool RELAXED>
-__global__ void ccl2_seam_kernel(const uint8_t* __restrict__ fg, int* L, int H, int W, int tiles_x, int tiles_y, const int* __restrict__ cols = nullptr) {
+__global__ void ccl2_seam_kernel(const uint8_t* __restrict__ fg, int* L, int H, int W, int tiles_x, int tiles_y, const int* __restrict__ cols) {
     const unsigned sx = (unsigned)(tiles_x - 1), sy = (unsigned)(tiles_y - 1);
     const unsigned nv = sx * (unsigned)H, nh = sy * (unsigned)W;
     const unsigned total = nv + nh, stride = gridDim.x * blockDim.x;
@@ -645,18 +583,11 @@ __global__ void ccl2_seam_kernel(const uint8_t* __restrict__ fg, int* L, int H, 
         const unsigned i = i0 + lane;
         int a = -1, b = -1;
         int ca = -1, cb = -1;  // vertical seam through the compact columns (two colours: bit 31)
-        if (i < nv && cols) {
+        if (i < nv) {
             const int va = cols[i], vb = cols[nv + i];
             if ((va ^ vb) >= 0) {  // same colour
                 ca = va & 0x7fffffff;
                 cb = vb & 0x7fffffff;
-            }
-        } else if (i < nv) {
-            const unsigned k = i / (unsigned)H, y = i - k * (unsigned)H, x = (k + 1) * CT_W;
-            const long long p = (long long)y * W + x;
-            if ((fg[p] != 0) == (fg[p - 1] != 0)) {
-                a = (int)p;
-                b = (int)p - 1;
             }
         } else if (i < total) {
             const unsigned j = i - nv;
@@ -674,10 +605,7 @@ __global__ void ccl2_seam_kernel(const uint8_t* __restrict__ fg, int* L, int H, 
         }
         const int ra = ca >= 0 ? ca : a >= 0 ? L[a] : -1, rb = ca >= 0 ? cb : b >= 0 ? L[b] : -2;  // (see ccl_seam_kernel: one union per run of equal root pairs)
         const int pa = __shfl_up(ra, 1), pb = __shfl_up(rb, 1);
-        if ((a >= 0 || ca >= 0) && ra != rb && !(lane > 0 && pa == ra && pb == rb)) {
-            if (RELAXED) uf_union_relaxed(L, ra, rb);
-            else uf_union(L, ra, rb);
-        }
+        if ((a >= 0 || ca >= 0) && ra != rb && !(lane > 0 && pa == ra && pb == rb)) uf_union_relaxed(L, ra, rb);
     }
 }
 // foreground components below min_size turn into background and join the background sets around them
@@ -727,13 +655,10 @@ __global__ void ccl2_fill_kernel(uint8_t* m, int* L, const int* __restrict__ bor
         if (y < H - 1 && m[p + W]) uf_union(L, (int)p, (int)(p + W));
     }
 }
-// final marker labels: root for foreground pixels, -1 for the background
-__global__ void ccl2_final_kernel(int* L, const uint8_t* __restrict__ m, int n) {
-    // (flattened roots: L[L[p]] is the root; a foreground node that other pixels still point at keeps the value it already holds)
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) L[p] = m[p] ? L[L[p]] : -1;
-}
-// the same, and bits[p >> 6] |= "p is the root of a marker" (whole waves step together: the ballot covers 64 consecutive pixels)
+// final marker labels: root for foreground pixels, -1 for the background, and bits[p >> 6] |= "p is the root of a marker" (whole waves step
+// together: the ballot covers 64 consecutive pixels)
 __global__ void ccl2_final_bits_kernel(int* L, const uint8_t* __restrict__ m, int n, u64* __restrict__ bits) {
+    // (flattened roots: L[L[p]] is the root; a foreground node that other pixels still point at keeps the value it already holds)
     const int lane = threadIdx.x & 63;
     for (long long base = (blockIdx.x * (long long)blockDim.x + threadIdx.x) - lane; base < n; base += (long long)gridDim.x * blockDim.x) {
         const long long p = base + lane;
@@ -789,40 +714,7 @@ __global__ void ccl2_drop_small4_kernel(uint32_t* m4, int4* L4, const int* __res
         }
     }
 }
-__global__ void ccl2_fill4_kernel(uint32_t* m4, int4* L4, const int* __restrict__ border, int H, int W) {
-    const long long nq = (long long)H * W / 4;
-    const int qw = W / 4;
-    const double invQ = 1.0 / (double)qw;
-    uint8_t* m = (uint8_t*)m4;
-    int* L = (int*)L4;
-    for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
-        const uint32_t mw = m4[q];
-        if (mw == 0x01010101u) continue;
-        const int4 l = L4[q];
-        const int t[4] = {l.x, l.y, l.z, l.w};
-        int pt = -1;
-        bool hole = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if ((mw >> (8 * i)) & 0xffu) continue;
-            if (t[i] != pt) {
-                pt = t[i];
-                hole = !border[uf_find(L, pt)];
-            }
-            if (!hole) continue;
-            int y, xq;
-            pix_yx(q, qw, invQ, y, xq);
-            const int x = xq * 4 + i;
-            const long long p = q * 4 + i;
-            m[p] = 1;
-            if (x > 0 && m[p - 1]) uf_union(L, (int)p, (int)p - 1);
-            if (x < W - 1 && m[p + 1]) uf_union(L, (int)p, (int)p + 1);
-            if (y > 0 && m[p - W]) uf_union(L, (int)p, (int)(p - W));
-            if (y < H - 1 && m[p + W]) uf_union(L, (int)p, (int)(p + W));
-        }
-    }
-}
-// The same fill, gated per TILE (round 6): a hole is a background set that does not reach the border, and every pixel of it belongs to a tile-local set whose
+// The fill with four pixels per thread, gated per TILE (round 6): a hole is a background set that does not reach the border, and every pixel of it belongs to a tile-local set whose
 // tile root sits in that tile's range of the root list -- so a tile none of whose list entries is background with an unflagged root holds no hole pixel and is
 // skipped without touching its labels (holes are rare: 5.0 -> ~0.5 B/px of a call, the pass 0.155 -> ~0.03 ms at 8192^2).  One wave per tile; the list is flat
 // here (ccl2_flatten_roots_kernel ran after the last unions), so L[entry] is the entry's root.
@@ -941,8 +833,9 @@ __global__ void apply_min_area_bits4_kernel(uint32_t* __restrict__ m4, int4* L4,
     }
 }
 // roots: H * W ints (every tile its own range), n_roots: one int per tile
+// root_bits: bitmap of the final markers' roots; colbuf: 2 x (tiles_x - 1) x H ints for the seam columns; wide: four pixels per thread (W % 4 == 0)
 static int markers_two_colour(uint8_t* mrk, int* L, int* area, int* border, int* roots, int* n_roots, int min_size, int H, int W, hipStream_t st,
-                              u64* root_bits = nullptr, bool wide = false, int* colbuf = nullptr) {
+                              u64* root_bits, bool wide, int* colbuf) {
     const int n = H * W;
     const int tiles_x = (W + CT_W - 1) / CT_W, tiles_y = (H + CT_H - 1) / CT_H, n_tiles = tiles_x * tiles_y;
     const unsigned g = grid_for(n);
@@ -950,45 +843,25 @@ static int markers_two_colour(uint8_t* mrk, int* L, int* area, int* border, int*
     //  root list's entries by the first flatten pass below)
     hipLaunchKernelGGL(ccl2_tile_kernel, dim3(n_tiles < 256 * 16 ? n_tiles : 256 * 16), dim3(256), 0, st, mrk, L, H, W, tiles_x, n_tiles, roots, n_roots, area, colbuf);
     const long long seams = (long long)(tiles_x - 1) * H + (long long)(tiles_y - 1) * W;
-    static const bool seam_relaxed = cerb_dev_getenv("CERB_PP_SEAM_STRICT") == nullptr;
-    if (seams > 0) hipLaunchKernelGGL(seam_relaxed ? ccl2_seam_kernel<true> : ccl2_seam_kernel<false>, dim3(grid_for(seams)), dim3(256), 0, st, mrk, L, H, W, tiles_x, tiles_y, (const int*)colbuf);
+    if (seams > 0) hipLaunchKernelGGL(ccl2_seam_kernel, dim3(grid_for(seams)), dim3(256), 0, st, mrk, L, H, W, tiles_x, tiles_y, (const int*)colbuf);
     const unsigned gl = nblk(n_tiles, 4) < 4096 ? nblk(n_tiles, 4) : 4096;  // one wave per tile
     auto flatten_roots = [&]() { hipLaunchKernelGGL(ccl2_flatten_roots_kernel, dim3(gl), dim3(256), 0, st, L, (const int*)roots, (const int*)n_roots, n_tiles, tiles_x, H, W, (int*)nullptr); };
     hipLaunchKernelGGL(ccl2_flatten_roots_kernel, dim3(gl), dim3(256), 0, st, L, (const int*)roots, (const int*)n_roots, n_tiles, tiles_x, H, W, border);
     hipLaunchKernelGGL(roots_area_merge_kernel, dim3(gl), dim3(256), 0, st, (const int*)L, (const int*)roots, (const int*)n_roots, n_tiles, tiles_x, H, W, area);
-    wide = wide && W % 4 == 0;
     const unsigned g4 = grid_for(n / 4);
     if (wide) hipLaunchKernelGGL(ccl2_drop_small4_kernel, dim3(g4), dim3(256), 0, st, (uint32_t*)mrk, (int4*)L, area, min_size, H, W);
     else hipLaunchKernelGGL(ccl2_drop_small_kernel, dim3(g), dim3(256), 0, st, mrk, L, area, min_size, H, W);
     flatten_roots();
     hipLaunchKernelGGL(ccl2_mark_border_kernel, dim3(nblk(2 * (H + W), 256)), dim3(256), 0, st, mrk, L, border, H, W);
-    static const bool fill_by_tile = cerb_dev_getenv("CERB_PP_FILL_WHOLE_MAP") == nullptr;  // developers' build: =1 keeps round 5's pass over every quad
-    if (wide && fill_by_tile) hipLaunchKernelGGL(ccl2_fill_tiles4_kernel, dim3(gl), dim3(256), 0, st, (uint32_t*)mrk, (int4*)L, border, (const int*)roots, (const int*)n_roots, n_tiles, tiles_x, H, W);
-    else if (wide) hipLaunchKernelGGL(ccl2_fill4_kernel, dim3(g4), dim3(256), 0, st, (uint32_t*)mrk, (int4*)L, border, H, W);
+    if (wide) hipLaunchKernelGGL(ccl2_fill_tiles4_kernel, dim3(gl), dim3(256), 0, st, (uint32_t*)mrk, (int4*)L, border, (const int*)roots, (const int*)n_roots, n_tiles, tiles_x, H, W);
     else hipLaunchKernelGGL(ccl2_fill_kernel, dim3(g), dim3(256), 0, st, mrk, L, border, H, W);
     flatten_roots();
-    if (root_bits && wide) hipLaunchKernelGGL(ccl2_final_bits4_kernel, dim3(g4), dim3(256), 0, st, (int4*)L, (const uint32_t*)mrk, (long long)n / 4, root_bits);
-    else if (root_bits) hipLaunchKernelGGL(ccl2_final_bits_kernel, dim3(g), dim3(256), 0, st, L, mrk, n, root_bits);
-    else hipLaunchKernelGGL(ccl2_final_kernel, dim3(g), dim3(256), 0, st, L, mrk, n);
+    if (wide) hipLaunchKernelGGL(ccl2_final_bits4_kernel, dim3(g4), dim3(256), 0, st, (int4*)L, (const uint32_t*)mrk, (long long)n / 4, root_bits);
+    else hipLaunchKernelGGL(ccl2_final_bits_kernel, dim3(g), dim3(256), 0, st, L, mrk, n, root_bits);
     KCHECK();
     return 0;
 }
 
-// area[root] += 1 for every labelled pixel (wave-aggregated when the whole wave sits in one component)
-__global__ void ccl_area_kernel(const int* __restrict__ L, int* __restrict__ area, int n) {
-    for (long long p0 = blockIdx.x * (long long)blockDim.x; p0 < n; p0 += (long long)gridDim.x * blockDim.x) {
-        const long long p = p0 + threadIdx.x;
-        const int r = (p < n) ? L[p] : -1;
-        const int r0 = __shfl(r, __ffsll((long long)__ballot(r >= 0)) - 1);
-        const u64 same = __ballot(r >= 0 && r == r0);
-        if (r >= 0) {
-            if (r == r0) {
-                if ((threadIdx.x & 63) == __ffsll((long long)same) - 1) atomicAdd(&area[r], __popcll(same));
-            } else
-                atomicAdd(&area[r], 1);
-        }
-    }
-}
 // flag[p] = 1 for roots of components with area >= min_size (0 otherwise / non-roots)
 __global__ void ccl_keep_roots_kernel(const int* __restrict__ L, const int* __restrict__ area, int min_size, int* __restrict__ flag, int n) {
     for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
@@ -1001,17 +874,8 @@ __global__ void ccl_relabel_kernel(const int* __restrict__ L, const int* __restr
         out[p] = (r >= 0 && flag[r]) ? rank[r] + 1 : 0;
     }
 }
-// the watershed's start map in one pass: out[p] = mask ? 1 + rank[root of p in the marker labelling] : 0 (rank = exclusive scan of "is a root");
-// replaces the flag pass, the relabel pass into a marker map and the mask pass over it
-// (boff: the scan's per-1024 block offsets, left unadded by scan_exclusive(..., &boff); nullptr = already complete)
-__global__ void nuc_marker_out_kernel(const int* __restrict__ L, const int* __restrict__ rank, const int* __restrict__ boff, const uint8_t* __restrict__ mask,
-                                      int* __restrict__ out, int n) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
-        const int r = L[p];
-        out[p] = (r >= 0 && mask[p]) ? rank[r] + (boff ? boff[r / SCAN_ITEMS] : 0) + 1 : 0;
-    }
-}
-// the same from the root bitmap: label = 1 + number of roots before the pixel's root in raster order.
+// the watershed's start map in one pass: out[p] = mask ? 1 + rank of the root of p in the marker labelling : 0, the rank taken from the root bitmap
+// (number of roots before the pixel's root in raster order; boff: the per-1024-word block offsets scan_exclusive_popc left unadded, or nullptr).
 // Also the smallest / largest marker label inside every mask component (lmin / lmax at the component's root LA[p]; roots_setup_kernel has initialised
 // them): one pair of atomics per RUN of equal (label, component) inside a wave, and only where a plain read does not already cover the label (the
 // extremes are monotone, a stale read costs an atomic, never a miss).  Taken over all labelled pixels this equals the extremes over the SEEDS (labelled
@@ -1091,11 +955,6 @@ __global__ void count_roots_from_bits_kernel(const u64* __restrict__ bits, const
                                              const int* __restrict__ any) {
     if (blockIdx.x == 0 && threadIdx.x == 0)
         *out = (any && !*any) ? -1 : (nw > 0 ? wpre[nw - 1] + (boff ? boff[(nw - 1) / SCAN_ITEMS] : 0) + __popcll(bits[nw - 1]) : 0);
-}
-__global__ void count_roots_from_scan_kernel(const int* __restrict__ L, const int* __restrict__ rank, const int* __restrict__ boff, int n, int* __restrict__ out,
-                                             const int* __restrict__ any) {
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *out = (any && !*any) ? -1 : (n > 0 ? rank[n - 1] + (boff ? boff[(n - 1) / SCAN_ITEMS] : 0) + (L[n - 1] == n - 1 ? 1 : 0) : 0);
 }
 __global__ void count_from_scan_kernel(const int* __restrict__ flag, const int* __restrict__ rank, int n, int* __restrict__ out,
                                        const int* __restrict__ any) {
@@ -1195,14 +1054,7 @@ __global__ void erode_cross_kernel(const uint8_t* __restrict__ src, uint8_t* __r
         dst[p] = v;
     }
 }
-// m[p] &= area[root(p)] >= min_size
-__global__ void apply_min_area_kernel(uint8_t* __restrict__ m, const int* __restrict__ L, const int* __restrict__ area, int min_size, int n) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
-        const int r = L[p];
-        m[p] = (r >= 0 && area[r] >= min_size) ? 1 : 0;
-    }
-}
-// the same, and bits[p >> 6] |= "p is the root of a kept component"
+// m[p] &= area[root(p)] >= min_size, and bits[p >> 6] |= "p is the root of a kept component"
 __global__ void apply_min_area_bits_kernel(uint8_t* __restrict__ m, const int* __restrict__ L, const int* __restrict__ area, int min_size, int n,
                                            u64* __restrict__ bits) {
     const int lane = threadIdx.x & 63;
@@ -1217,26 +1069,6 @@ __global__ void apply_min_area_bits_kernel(uint8_t* __restrict__ m, const int* _
         }
         const u64 b = __ballot(root);
         if (lane == 0) bits[base >> 6] = b;
-    }
-}
-// border[root] = 1 for background components touching the border of the H x W domain
-__global__ void mark_border_kernel(const int* __restrict__ L, int* __restrict__ border, int H, int W) {
-    const int per = 2 * (H + W);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) {
-        long long p;
-        if (i < W) p = i;
-        else if (i < 2 * W) p = (long long)(H - 1) * W + (i - W);
-        else if (i < 2 * W + H) p = (long long)(i - 2 * W) * W;
-        else p = (long long)(i - 2 * W - H) * W + (W - 1);
-        const int r = L[p];
-        if (r >= 0) border[r] = 1;
-    }
-}
-// m[p] |= (background component of p does not touch the border)     (scipy.ndimage.binary_fill_holes)
-__global__ void fill_holes_apply_kernel(uint8_t* __restrict__ m, const int* __restrict__ L, const int* __restrict__ border, int n) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
-        const int r = L[p];
-        if (r >= 0 && !border[r]) m[p] = 1;
     }
 }
 
@@ -1255,22 +1087,11 @@ __device__ __forceinline__ u32 order_key(float v) {  // monotone map float -> ui
 #define WS_UNC32 0x80000000u
 #define WS_UNC16 0x8000u
 
-// out[p] = mask ? marker : 0 ; per mask component: count of pixels that can ever enter the queue (upper bound of the
-// heap size = component area) is already known (area).  Seeds = labelled pixels with an unlabelled in-mask neighbour.
-__global__ void ws_init_out_kernel(const uint8_t* __restrict__ mask, const int* __restrict__ marker, int* __restrict__ out, int n) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
-        out[p] = mask[p] ? marker[p] : 0;
-}
-// heap capacity per component root = its area (kept components only)
-__global__ void ws_cap_kernel(const int* __restrict__ L, const int* __restrict__ area, const uint8_t* __restrict__ mask, int* __restrict__ cap, int n) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
-        cap[p] = (L[p] == (int)p && mask[p]) ? area[p] : 0;
-}
 __global__ void ws_seed_kernel(const float* __restrict__ inst, long long row_stride, int pix_stride, const uint8_t* __restrict__ mask,
                                const int* __restrict__ out, const int* __restrict__ L, const int* __restrict__ hoff, int* __restrict__ hcnt,
-                               u64* __restrict__ hkey, u32* __restrict__ hidx, int H, int W, int* __restrict__ unl, int* __restrict__ lmin,
-                               int* __restrict__ lmax, int known) {
-    // known: lmin / lmax are final already (nuc_marker_out_bits_kernel): components whose markers carry ONE label never reach a flood
+                               u64* __restrict__ hkey, u32* __restrict__ hidx, int H, int W, int* __restrict__ unl, const int* __restrict__ lmin,
+                               const int* __restrict__ lmax) {
+    // lmin / lmax are final already (nuc_marker_out_bits_kernel): components whose markers carry ONE label never reach a flood
     // (ws_fill_single_kernel paints them), so neither their seeds nor their floodable-pixel counts are wanted -- isolated nuclei issue no atomic here
     const long long n = (long long)H * W;
     const double invW = 1.0 / (double)W;
@@ -1285,7 +1106,7 @@ __global__ void ws_seed_kernel(const float* __restrict__ inst, long long row_str
         const int prev = __shfl_up(key, 1);
         const bool head = key >= 0 && (lane == 0 || prev != key);
         const unsigned long long bounds = __ballot(head || key < 0);
-        if (head && (!known || lmin[key] < lmax[key])) {
+        if (head && lmin[key] < lmax[key]) {
             const unsigned long long after = lane == 63 ? 0ull : (bounds >> (lane + 1));
             const int run = after ? __ffsll((long long)after) : 64 - lane;
             atomicAdd(&unl[key], run);
@@ -1300,12 +1121,7 @@ __global__ void ws_seed_kernel(const float* __restrict__ inst, long long row_str
         if (y < H - 1 && mask[p + W] && !out[p + W]) active = true;
         if (!active) continue;
         const int root = L[p];
-        if (known) {
-            if (lmin[root] >= lmax[root]) continue;
-        } else {
-            atomicMin(&lmin[root], out[p]);
-            atomicMax(&lmax[root], out[p]);
-        }
+        if (lmin[root] >= lmax[root]) continue;
         const int slot = hoff[root] + atomicAdd(&hcnt[root], 1);
         const float v = -inst[y * row_stride + (long long)x * pix_stride];  // watershed(-inst_inner_raw, ...)
         hkey[slot] = ((u64)order_key(v) << 32);  // age 0
@@ -1316,12 +1132,7 @@ __global__ void ws_seed_kernel(const float* __restrict__ inst, long long row_str
 struct CBox {
     int y1, y2, x1, x2;  // inclusive
 };
-__global__ void ws_bbox_init_kernel(const int* __restrict__ L, const uint8_t* __restrict__ mask, CBox* __restrict__ bb, int H, int W) {
-    const long long n = (long long)H * W;
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
-        if (L[p] == (int)p && mask[p]) bb[p] = CBox{H, -1, W, -1};
-}
-// Only components that reach a priority flood need their box (ws_worklist_kernel: seeds of at least two labels, lmin < lmax; no seed at all
+// Only components that reach a priority flood need their box (ws_worklist_bits_kernel: seeds of at least two labels, lmin < lmax; no seed at all
 // leaves lmin = 0x7f7f7f7f > lmax = 0): isolated nuclei -- the common case -- skip the outline test and the atomics.
 __global__ void ws_bbox_kernel(const int* __restrict__ L, const uint8_t* __restrict__ mask, CBox* bb, int H, int W, const int* __restrict__ lmin,
                                const int* __restrict__ lmax) {
@@ -1481,68 +1292,11 @@ __global__ void ws_seed_bbox4_kernel(const float* __restrict__ inst, long long r
 // A component all of whose seeds carry ONE label needs no priority flood: every unlabelled mask pixel of a 4-connected mask
 // component is reachable from a seed through unlabelled mask pixels, so the flood can only ever assign that label
 // (ws_fill_single_kernel).  Isolated nuclei -- the common case -- take this path; only touching clusters reach the heaps.
-// First kernel of the heap-offset scan with the per-root state set up on the way: the scanned value is the heap capacity of a kept mask component
-// (its area, at its root pixel; 0 elsewhere), and every kept root gets its counters / label extremes / box initialised HERE -- the per-root arrays are
-// indexed by root pixel and only ever read at kept roots, so the four whole-map fills, the capacity pass and the box-init pass are not needed.
-__global__ __launch_bounds__(256) void scan_block_cap_kernel(const int* __restrict__ L, const int* __restrict__ area, const uint8_t* __restrict__ mask,
-                                                            int* __restrict__ out, int* __restrict__ sums, int n, int* __restrict__ hcnt, int* __restrict__ unl,
-                                                            int* __restrict__ lmin, int* __restrict__ lmax, CBox* __restrict__ bb, int H, int W) {
-    __shared__ int wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long base = (long long)blockIdx.x * SCAN_ITEMS + tid * 4;
-    int v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long long j = base + i;
-        v[i] = 0;
-        if (j < n && L[j] == (int)j && mask[j]) {
-            v[i] = area[j];
-            hcnt[j] = 0;
-            unl[j] = 0;
-            lmin[j] = 0x7f7f7f7f;
-            lmax[j] = 0;
-            bb[j] = CBox{H, -1, W, -1};
-        }
-    }
-    const int tsum = v[0] + v[1] + v[2] + v[3];
-    int inc = tsum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    int run = woff + inc - tsum;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (base + i < n) out[base + i] = run;
-        run += v[i];
-    }
-    if (tid == 255 && sums) sums[blockIdx.x] = woff + inc;
-}
-__global__ void ws_worklist_kernel(const int* __restrict__ hcnt, const int* __restrict__ area, const int* __restrict__ unl, const CBox* __restrict__ bb,
-                                   const int* __restrict__ lmin, const int* __restrict__ lmax, int* __restrict__ wl, int* __restrict__ wl2,
-                                   int* __restrict__ wl3, int* __restrict__ wl4, int* __restrict__ counts, int n, const int* __restrict__ L,
-                                   const uint8_t* __restrict__ mask) {
-    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
-        if (L[p] == (int)p && mask[p] && hcnt[p] > 0 && lmin[p] != lmax[p]) {  // (the per-root arrays hold something at kept roots only)
-            const CBox b = bb[p];
-            const long long win = (long long)(b.y2 - b.y1 + 3) * (b.x2 - b.x1 + 3);
-            const int need = hcnt[p] + unl[p];  // every queue entry is a seed or a pixel that was unlabelled at the start
-            if (need <= WS_TINY_CAP && win <= WS_TINY_WIN) wl4[atomicAdd(counts + 4, 1)] = (int)p;
-            else if (need <= WS_LDS_CAP && win <= WS_WIN_CAP) wl[atomicAdd(counts + 0, 1)] = (int)p;
-            else if (need <= WS_BIGHEAP_CAP && win <= WS_BIGWIN_CAP) wl3[atomicAdd(counts + 3, 1)] = (int)p;
-            else if (area[p] <= WS_LDS_CAP) wl2[atomicAdd(counts + 1, 1)] = (int)p;
-            else wl[n - 1 - atomicAdd(counts + 2, 1)] = (int)p;
-        }
-}
 
 // Per-component setup over the root bitmap (one thread per 64-pixel word): counters, label extremes, box, and the heap offset -- any disjoint
 // partition of the heap arrays will do (the floods address their heap as hoff[root] + i), so a block adds the areas of its roots up and takes its
-// range with ONE atomic; the exclusive scan over the pixel map (scan_block_cap_kernel + two small scans + a whole-map add) is not needed.
+// range with ONE atomic; no exclusive scan over the pixel map is needed.  The per-root arrays are indexed by root pixel and only ever read at kept roots, so
+// initialising them HERE replaces four whole-map fills.
 __global__ __launch_bounds__(256) void roots_setup_kernel(const u64* __restrict__ bits, int nw, const int* __restrict__ area, int* __restrict__ hoff,
                                                           int* __restrict__ hcnt, int* __restrict__ unl, int* __restrict__ lmin, int* __restrict__ lmax,
                                                           CBox* __restrict__ bb, int H, int W, int* __restrict__ total) {
@@ -1588,7 +1342,7 @@ __global__ void ws_worklist_bits_kernel(const u64* __restrict__ bits, int nw, co
             if (!(hcnt[p] > 0 && lmin[p] != lmax[p])) continue;
             const CBox b = bb[p];
             const long long win = (long long)(b.y2 - b.y1 + 3) * (b.x2 - b.x1 + 3);
-            const int need = hcnt[p] + unl[p];
+            const int need = hcnt[p] + unl[p];  // every queue entry is a seed or a pixel that was unlabelled at the start
             if (need <= WS_TINY_CAP && win <= WS_TINY_WIN) wl4[atomicAdd(counts + 4, 1)] = p;
             else if (need <= WS_LDS_CAP && win <= WS_WIN_CAP) wl[atomicAdd(counts + 0, 1)] = p;
             else if (need <= WS_BIGHEAP_CAP && win <= WS_BIGWIN_CAP) wl3[atomicAdd(counts + 3, 1)] = p;
@@ -2451,7 +2205,7 @@ __global__ __launch_bounds__(256) void gl_bg_merge_kernel(const uint8_t* __restr
         const int x = i % cw;
         const bool left = x > 0 && !dil[e - 1];
         if (i >= cw && !dil[e - cw]) {
-            // one union per pair of vertically adjacent background runs (see ccl_merge_kernel)
+            // one union per pair of vertically adjacent background runs: at the first column where they overlap either the lower run starts here, or the upper one does
             const bool up_starts = !(x > 0 && !dil[e - cw - 1]);
             if (!left || up_starts) uf_union(L, e, e - cw);
         }
@@ -2574,9 +2328,9 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
     Carve cv{(char*)ws, ws_bytes};
     int* LA = (int*)cv.take((size_t)n * 4);     // mask components
     int* areaA = (int*)cv.take((size_t)n * 4);
-    int* LB = (int*)cv.take((size_t)n * 4);     // scratch CCL (markers, background, filled markers)
-    int* areaB = (int*)cv.take((size_t)n * 4);  // also: border flags, root flags
-    int* rank = (int*)cv.take((size_t)n * 4);
+    int* LB = (int*)cv.take((size_t)n * 4);     // marker components (both colours until the markers are final)
+    int* areaB = (int*)cv.take((size_t)n * 4);
+    int* rank = (int*)cv.take((size_t)n * 4);   // the markers' border flags, then the LDS-heap tier list
     int* marker = (int*)cv.take((size_t)n * 4);
     int* hoff = (int*)cv.take((size_t)n * 4);
     int* hcnt = (int*)cv.take((size_t)n * 4);
@@ -2589,23 +2343,26 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
     uint8_t* mrk = (uint8_t*)cv.take(n);
     int* scantmp = (int*)cv.take((size_t)(n / SCAN_ITEMS + 4096) * 4 * 2);
     int* wl4 = (int*)cv.take((size_t)n * 4);    // tiny-window tier list
-    int* lmax = (int*)cv.take((size_t)n * 4);   // per mask component: largest seed label (smallest one lives in LB once the markers are final)
+    int* lmax = (int*)cv.take((size_t)n * 4);   // per mask component: largest marker label
     const int nw = (n + 63) / 64;               // root bitmaps: one bit per pixel
     u64* bitsA = (u64*)cv.take((size_t)nw * 8); // kept mask components
     u64* bitsB = (u64*)cv.take((size_t)nw * 8); // final markers
     int* wpre = (int*)cv.take((size_t)nw * 4);  // roots before a bitmap word
-    int* lminbuf = (int*)cv.take((size_t)n * 4); // per mask component: smallest marker label (written while LB is still read)
+    int* lmin = (int*)cv.take((size_t)n * 4);   // per mask component: smallest marker label
     int* tcnt = (int*)cv.take((size_t)(((W + CT_W - 1) / CT_W) * ((H + CT_H - 1) / CT_H)) * 4);  // roots per labelling tile
-    int* small = (int*)cv.take(256);  // [0]=any [1]=worklist count [2]=n_inst scratch [3]=ambiguous scratch [4]=two-colour root list [8..12]=tier counts [16]=heap total
+    int* small = (int*)cv.take(256);  // [0]=any [1]=worklist count [2]=n_inst scratch [3]=ambiguous scratch [8..12]=tier counts [16]=heap total
     if (!small) return cerb_set_error("cerb_postproc_nuclei: workspace carve failed");
     const unsigned g = grid_for(n);
-    static const bool pixel_scans = cerb_dev_getenv("CERB_PP_PIXEL_SCANS") != nullptr;  // developer A/B: round 4's whole-map scans instead of the root bitmaps
+    // Four pixels per thread want whole quads per row and 16-byte aligned maps (the workspace arrays are 256-byte aligned); every other map takes the
+    // one-pixel-per-thread passes, and CERB_PP_ONE_PIXEL_THREADS (developers' build) sends any map through them so that a test can hold both to the same bytes.
+    static const bool narrow = cerb_dev_getenv("CERB_PP_ONE_PIXEL_THREADS") != nullptr;
+    const bool wide = !narrow && W % 4 == 0 && (uintptr_t)labels_out % 16 == 0;
 
     PP_OK(hipMemsetAsync(small, 0, 256, st));
     // (A) mask: erode -> label -> drop components < 8 px   (postproc.py:365-368)
     // (round 5 tried threshold + erosion + tile labelling as ONE kernel over a 66 x 34 window per tile: bit-exact, 0.68 ms against 0.51 ms for the three
     // launches below -- the 8-byte loads, the divergent halo columns and three barriers per tile cost more than the two byte planes it saved)
-    if (W % 4 == 0 && ((uintptr_t)msk0 | (uintptr_t)msk | (uintptr_t)mrk) % 4 == 0) {
+    if (W % 4 == 0 && ((uintptr_t)msk0 | (uintptr_t)msk | (uintptr_t)mrk) % 4 == 0) {  // (these two touch workspace maps only: `labels_out` does not matter to them)
         const unsigned g4 = grid_for(n / 4);
         const bool packed = pix_stride == 2 && row_stride % 4 == 0 && (uintptr_t)inst % 16 == 0;
         hipLaunchKernelGGL(packed ? nuc_threshold4_kernel<true> : nuc_threshold4_kernel<false>, dim3(g4), dim3(256), 0, st, inst, row_stride, pix_stride, H, W,
@@ -2616,11 +2373,8 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
         hipLaunchKernelGGL(erode_cross_kernel, dim3(g), dim3(256), 0, st, msk0, msk, H, W);
     }
     // round 6: the tile labellings leave their border columns in a compact array (2 x (tiles_x - 1) x H ints: wl4 is free until the flood work lists) and the
-    // seam passes read their vertical seams from it -- CERB_PP_SEAM_COLUMNS=0 (developers' build) keeps the strided reads of the maps
-    static const bool seam_compact = cerb_dev_getenv("CERB_PP_SEAM_COLUMNS") == nullptr || atoi(cerb_dev_getenv("CERB_PP_SEAM_COLUMNS")) != 0;
-    int* seam_cols = seam_compact ? wl4 : nullptr;
-    static const bool narrow = cerb_dev_getenv("CERB_PP_ONE_PIXEL_THREADS") != nullptr;  // developer A/B: the one-pixel-per-thread passes
-    const bool wide = !pixel_scans && !narrow && W % 4 == 0 && (uintptr_t)labels_out % 16 == 0;  // (the workspace arrays are 256-byte aligned)
+    // seam passes read their vertical seams from it
+    int* seam_cols = wl4;
     if (wide) {  // tile labelling with the root list + per-set counts, flatten and areas over the LIST, then one pass: min-area, root of every pixel, bitmap
         int* rootsA = hoff;       // free until roots_setup_kernel
         int* n_rootsA = tcnt;     // roots per tile
@@ -2637,70 +2391,36 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
     } else {
         PP_OK(hipMemsetAsync(areaA, 0, (size_t)n * 4, st));
         if (ccl_run(msk, 1, LA, H, W, st, areaA)) return 1;
-        if (pixel_scans) hipLaunchKernelGGL(apply_min_area_kernel, dim3(g), dim3(256), 0, st, msk, LA, areaA, 8, n);
-        else hipLaunchKernelGGL(apply_min_area_bits_kernel, dim3(g), dim3(256), 0, st, msk, LA, areaA, 8, n, bitsA);
+        hipLaunchKernelGGL(apply_min_area_bits_kernel, dim3(g), dim3(256), 0, st, msk, LA, areaA, 8, n, bitsA);
     }
     // (B) markers: inner > 0.5 -> label -> drop < 4 px -> fill holes -> label (postproc.py:370-377)
-    static const bool three_pass = cerb_dev_getenv("CERB_PP_THREE_LABELLINGS") != nullptr;  // developer A/B: round 4's three separate labellings
-    if (!three_pass) {
-        // (rank: free until the scan below, serves as the border flags; marker: free until the flood work lists, holds the root list)
-        if (markers_two_colour(mrk, LB, areaB, rank, marker, tcnt, 4, H, W, st, pixel_scans ? nullptr : bitsB, wide, seam_cols)) return 1;
-    } else {
-        PP_OK(hipMemsetAsync(areaB, 0, (size_t)n * 4, st));
-        if (ccl_run(mrk, 1, LB, H, W, st, areaB)) return 1;
-        hipLaunchKernelGGL(apply_min_area_kernel, dim3(g), dim3(256), 0, st, mrk, LB, areaB, 4, n);
-        if (ccl_run(mrk, 0, LB, H, W, st)) return 1;  // background of the marker image
-        PP_OK(hipMemsetAsync(areaB, 0, (size_t)n * 4, st));
-        hipLaunchKernelGGL(mark_border_kernel, dim3(nblk(2 * (H + W), 256)), dim3(256), 0, st, LB, areaB, H, W);
-        hipLaunchKernelGGL(fill_holes_apply_kernel, dim3(g), dim3(256), 0, st, mrk, LB, areaB, n);
-        if (ccl_run(mrk, 1, LB, H, W, st)) return 1;
-    }
-    // marker ids = 1 + rank of the component's root among all roots (scipy's label order), written straight into the watershed's start map
-    const int* boff = nullptr;
-    const bool bitmaps = !pixel_scans && !three_pass;
+    // (rank: free until the flood work lists, serves as the border flags; marker: free until the flood work lists, holds the root list)
+    if (markers_two_colour(mrk, LB, areaB, rank, marker, tcnt, 4, H, W, st, bitsB, wide, seam_cols)) return 1;
+    // (C) per-component state and heap ranges from the mask's root bitmap, before the pass that fills in the label extremes
     int* unl = areaB;  // free again: per-root count of unlabelled mask pixels
     int* wl3 = marker; // big-window tier list
-    int* lmin = bitmaps ? lminbuf : LB;  // (LB: free after nuc_marker_out_kernel)
-    if (!pixel_scans && bitmaps) {  // per-component state and heap ranges from the root bitmap, before the pass that fills in the label extremes
-        hipLaunchKernelGGL(roots_setup_kernel, dim3(nblk(nw, 256)), dim3(256), 0, st, bitsA, nw, areaA, hoff, hcnt, unl, lmin, lmax, cbox, H, W, small + 16);
-        KCHECK();
-    }
-    if (bitmaps) {
-        if (scan_exclusive_popc(bitsB, wpre, nw, scantmp, st, &boff)) return 1;
-        if (n_inst_out) hipLaunchKernelGGL(count_roots_from_bits_kernel, dim3(1), dim3(1), 0, st, bitsB, wpre, boff, nw, n_inst_out, small);
-        // (C) watershed(-inner, marker, mask)   (postproc.py:378)
-        if (wide && bitmaps) hipLaunchKernelGGL(nuc_marker_out4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, (const int4*)LB, bitsB, wpre, boff, (const uint32_t*)msk, (int4*)labels_out,
-                                     (long long)n / 4, (const int4*)LA, lmin, lmax, (const uint32_t*)mrk);
-        else hipLaunchKernelGGL(nuc_marker_out_bits_kernel, dim3(g), dim3(256), 0, st, LB, bitsB, wpre, boff, msk, labels_out, n, LA, lmin, lmax);
-    } else {
-        if (scan_exclusive(LB, rank, n, scantmp, st, true, &boff)) return 1;
-        if (n_inst_out) hipLaunchKernelGGL(count_roots_from_scan_kernel, dim3(1), dim3(1), 0, st, LB, rank, boff, n, n_inst_out, small);
-        hipLaunchKernelGGL(nuc_marker_out_kernel, dim3(g), dim3(256), 0, st, LB, rank, boff, msk, labels_out, n);
-    }
-    if (!pixel_scans && !bitmaps) {  // (three separate labellings: the markers' L doubles as lmin, so the setup has to follow the start-map pass)
-        hipLaunchKernelGGL(roots_setup_kernel, dim3(nblk(nw, 256)), dim3(256), 0, st, bitsA, nw, areaA, hoff, hcnt, unl, lmin, lmax, cbox, H, W, small + 16);
-        KCHECK();
-    } else if (pixel_scans) {   // heap offsets = exclusive scan of the kept components' areas at their roots; the same pass initialises the per-root state
-        const int nbk = (n + SCAN_ITEMS - 1) / SCAN_ITEMS;
-        hipLaunchKernelGGL(scan_block_cap_kernel, dim3(nbk), dim3(256), 0, st, LA, areaA, msk, hoff, nbk > 1 ? scantmp : (int*)nullptr, n, hcnt, unl, lmin, lmax, cbox, H, W);
-        KCHECK();
-        if (nbk > 1) {
-            if (scan_exclusive(scantmp, scantmp, nbk, scantmp + ((nbk + 3) & ~3), st)) return 1;
-            hipLaunchKernelGGL(scan_add_kernel, dim3(nbk), dim3(256), 0, st, hoff, scantmp, n);
-            KCHECK();
-        }
-    }
-    if (wide && bitmaps) {
+    hipLaunchKernelGGL(roots_setup_kernel, dim3(nblk(nw, 256)), dim3(256), 0, st, bitsA, nw, areaA, hoff, hcnt, unl, lmin, lmax, cbox, H, W, small + 16);
+    KCHECK();
+    // marker ids = 1 + rank of the component's root among all roots (scipy's label order), written straight into the watershed's start map
+    const int* boff = nullptr;
+    if (scan_exclusive_popc(bitsB, wpre, nw, scantmp, st, &boff)) return 1;
+    if (n_inst_out) hipLaunchKernelGGL(count_roots_from_bits_kernel, dim3(1), dim3(1), 0, st, bitsB, wpre, boff, nw, n_inst_out, small);
+    if (wide) hipLaunchKernelGGL(nuc_marker_out4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, (const int4*)LB, bitsB, wpre, boff, (const uint32_t*)msk, (int4*)labels_out,
+                                 (long long)n / 4, (const int4*)LA, lmin, lmax, (const uint32_t*)mrk);
+    else hipLaunchKernelGGL(nuc_marker_out_bits_kernel, dim3(g), dim3(256), 0, st, LB, bitsB, wpre, boff, msk, labels_out, n, LA, lmin, lmax);
+    // (D) watershed(-inner, marker, mask)   (postproc.py:378): seeds, floodable-pixel counts and boxes of the components that reach a flood
+    if (wide) {
         hipLaunchKernelGGL(ws_seed_bbox4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, st, inst, row_stride, pix_stride, (const uint32_t*)msk, (const int4*)labels_out,
                            (const int4*)LA, hoff, hcnt, hkey, hidx, H, W, unl, lmin, lmax, cbox);
     } else {
         hipLaunchKernelGGL(ws_seed_kernel, dim3(g), dim3(256), 0, st, inst, row_stride, pix_stride, msk, labels_out, LA, hoff, hcnt, hkey, hidx, H, W, unl,
-                           lmin, lmax, bitmaps ? 1 : 0);
+                           lmin, lmax);
         hipLaunchKernelGGL(ws_bbox_kernel, dim3(g), dim3(256), 0, st, LA, msk, cbox, H, W, lmin, lmax);
     }
+    // (E) work lists, one per flood tier
     int* counts = small + 8;  // [0] window tier, [1] LDS-heap tier, [2] global tier
-    if (pixel_scans) hipLaunchKernelGGL(ws_worklist_kernel, dim3(g), dim3(256), 0, st, hcnt, areaA, unl, cbox, lmin, lmax, wl, rank, wl3, wl4, counts, n, LA, msk);
-    else hipLaunchKernelGGL(ws_worklist_bits_kernel, dim3(nblk(nw, 256) < 4096 ? nblk(nw, 256) : 4096), dim3(256), 0, st, bitsA, nw, hcnt, areaA, unl, cbox, lmin, lmax, wl, rank, wl3, wl4, counts, n);
+    hipLaunchKernelGGL(ws_worklist_bits_kernel, dim3(nblk(nw, 256) < 4096 ? nblk(nw, 256) : 4096), dim3(256), 0, st, bitsA, nw, hcnt, areaA, unl, cbox, lmin, lmax, wl, rank, wl3, wl4, counts, n);
+    // (F) floods
     {
         auto k_tiny = ws_flood_window_kernel<WS_TINY_WIN, WS_TINY_CAP, 4>;
         auto k_small = ws_flood_window_kernel<WS_WIN_CAP, WS_LDS_CAP, 2>;
@@ -2754,7 +2474,7 @@ extern "C" int cerb_postproc_nuclei(const float* inst, int H, int W, long long r
     }
     KCHECK();
     if (exact_ties) {
-        // Components whose result depends on skimage's heap-layout order between equal-valued markers were counted in small[3]:
+        // (G) exact replay.  Components whose result depends on skimage's heap-layout order between equal-valued markers were counted in small[3]:
         // when there is one, the whole map is re-flooded through the literal emulation of that heap (both kernels return at once
         // when the count is zero -- no host round trip decides this).
         constexpr int lds_exact = EX_LDS * 8 + 8 + EX_LDS * 4 + 4;

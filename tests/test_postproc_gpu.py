@@ -490,8 +490,7 @@ def _labels_digest(env_extra):
     import sys
 
     env = dict(os.environ)
-    for k in ("CERB_PP_ONE_PIXEL_THREADS", "CERB_PP_PIXEL_SCANS", "CERB_PP_SEAM_STRICT", "CERB_PP_THREE_LABELLINGS"):
-        env.pop(k, None)
+    env.pop("CERB_PP_ONE_PIXEL_THREADS", None)
     env.update(env_extra)
     env.pop("CERB_DEV_LIB", None)
     if env_extra:  # the switches exist only in the developers' build of the library (csrc/cerb_dev.h); the default run is the PRODUCT library's
@@ -504,9 +503,11 @@ def _labels_digest(env_extra):
 
 
 def test_every_front_variant_gives_the_same_labels():
-    """Round 5 rebuilt the nuclei front (root bitmaps, four pixels per thread, one seeds + counts + boxes pass, list-based areas, cached seam finds) and kept
-    the passes it replaces behind developer switches (read once per process: each variant runs in its own interpreter).  Every one of them must label three
-    seeded maps -- one with a width that is not a multiple of four, which takes the one-pixel passes anyway -- to the same bytes as the default."""
+    """The nuclei front has two schedules: four pixels per thread, and the one-pixel-per-thread passes that a map whose width is not a multiple of four
+    or whose label map is not 16-byte aligned takes.  CERB_PP_ONE_PIXEL_THREADS (developers' build; read once per process, so each variant runs in its own
+    interpreter) sends every map through the one-pixel passes behind the four-pixel threshold and erosion -- the mixed schedule a misaligned label map
+    gets.  It must label three seeded maps -- one with a width that is not a multiple of four, which takes the one-pixel passes throughout anyway -- to
+    the same bytes as the product library's default."""
     want = _labels_digest({})
-    for sw in ("CERB_PP_ONE_PIXEL_THREADS", "CERB_PP_PIXEL_SCANS", "CERB_PP_SEAM_STRICT", "CERB_PP_THREE_LABELLINGS"):
+    for sw in ("CERB_PP_ONE_PIXEL_THREADS",):
         assert _labels_digest({sw: "1"}) == want, sw
