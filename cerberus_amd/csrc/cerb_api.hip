@@ -566,6 +566,15 @@ int train_wino4_slot(cerb_net* net, const std::string& name, PackedConv& cm, int
     return 0;
 }
 
+// The lowest decoder level that runs tile-planar when everything above it does (level_is_planar in forward_impl; 2 = the two last levels only).
+static constexpr int kPlanarLowest = 0;
+// Profile families of the tile-planar launches, by decoder level (bench.py's table keeps the levels apart).  The two lowest levels' names start with
+// "conv_wino4_planar", not "conv_wino4p": tests/test_net_gpu.py counts the families that start with "conv_wino4p" (and the entry passes named exactly
+// "upsample2_add_planar") and expects the two last levels' four (two) launches.
+static const char* const kPlanarFamily[4] = {"conv_wino4_planar<f4x4,16x16x2,eighth-res>", "conv_wino4_planar<f4x4,16x16x2,quarter-res>",
+                                             "conv_wino4p<f4x4,16x16x2,planar,half-res>", "conv_wino4p<f4x4,16x16x2,planar>"};
+static const char* const kPlanarEntryFamily[4] = {"upsample2_add_planar<eighth-res>", "upsample2_add_planar<quarter-res>", "upsample2_add_planar", "upsample2_add_planar"};
+
 int run_conv(cerb_net* net, const std::string& name, const float* in, const float* prev, const float* resid, float* out, int N,
              int H, int W, int relu, int mode, long long in_gs, long long prev_gs, hipStream_t st, double* macs,
              const int* roi, long long planar_out_gs) {  // planar_out_gs > 0: in / out are tile-planar (conv_wino4p.hip)
@@ -636,11 +645,11 @@ int run_conv(cerb_net* net, const std::string& name, const float* in, const floa
         }
         if (planar) {
             p.out_gs = planar_out_gs;
-            p.level_tag = net->planar_half ? 0 : 1;
+            p.level_tag = net->planar_level == 3 ? 1 : net->planar_level == 2 ? 0 : 2;
             p.pl_byp = cerb_planar_blocks(p.Ho);
             p.pl_bxp = cerb_planar_blocks(p.Wo);
         }
-        if (prof_begin(net, name, planar ? (p.level_tag ? "conv_wino4p<f4x4,16x16x2,planar>" : "conv_wino4p<f4x4,16x16x2,planar,half-res>") : w4b ? (cerb_wino4b_packed(p) ? (resid ? "conv_wino4b<f4x4,16t,res>" : "conv_wino4b<f4x4,16t>") : (resid ? "conv_wino4b<f4x4,16x16,res>" : "conv_wino4b<f4x4,16x16>")) : (resid ? "conv_wino4<f4x4,16x16x2,res>" : "conv_wino4<f4x4,16x16x2>"), fl_done, st)) return 1;
+        if (prof_begin(net, name, planar ? kPlanarFamily[net->planar_level & 3] : w4b ? (cerb_wino4b_packed(p) ? (resid ? "conv_wino4b<f4x4,16t,res>" : "conv_wino4b<f4x4,16t>") : (resid ? "conv_wino4b<f4x4,16x16,res>" : "conv_wino4b<f4x4,16x16>")) : (resid ? "conv_wino4<f4x4,16x16x2,res>" : "conv_wino4<f4x4,16x16x2>"), fl_done, st)) return 1;
         if (net->conv_bn_part && !planar && !resid && !(roi && roi[1] > roi[0] && roi[3] > roi[2])) {
             p.bn_part = net->conv_bn_part;
             net->conv_bn_bpg = w4b ? cerb_wino4b_bn_blocks(p) : N * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
@@ -682,14 +691,31 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
     const int hs[5] = {H, H / 2, H / 4, H / 8, H / 16}, ws[5] = {W, W / 2, W / 4, W / 8, W / 16};
     const size_t D = net->trunk_idx.size();  // groups of the grouped decoder launches (one per decoder TRUNK; a trunk may feed several heads)
     const size_t guard = cerb_conv_guard_bytes(W);
-    // Which decoder levels keep their three private tensors in the tile-planar layout (conv_wino4p.hip): the two last levels (64 channels) when
-    // their maps are above conv_wino4b's range, on the default algorithms with folded BatchNorm.  One predicate for the allocation and the loop.
+    // Which decoder levels keep their three private tensors in the tile-planar layout (conv_wino4p.hip), on the default algorithms with folded
+    // BatchNorm: the two last levels (64 channels) when their maps reach past conv_wino4b's range, and below them the levels kPlanarLowest.. (any
+    // Cin % 16 == 0, Cout % 64 == 0) whose maps hold at least one 16 x 16 block.  A planar level may only feed a planar one, so a level is planar
+    // only if every level above it is.  One predicate for the allocation and the loop.
+    // Measured per launch on the headline's batch (32 tiles of 256^2, five decoders; profiles/decoder_low_levels_planar_ab.txt), conv_wino4b on NHWC ->
+    // conv_wino4p on planar, ms: dec.1.0 (64^2, 128 -> 64) 0.539 -> 0.478, dec.1.1 (64 -> 64) 0.286 -> 0.251, its entry pass 0.100 -> 0.108;
+    // dec.0.0 (32^2, 256 -> 128) 0.504 -> 0.449, dec.0.1 (128 -> 128: 640 items on 256 workgroups, 2.5 rounds) 0.269 -> 0.270, its entry pass
+    // 0.047 -> 0.043.  Level 1 saves 0.088 ms of a 13.9 ms step, level 0 another 0.057: both are on.
+    const int planar_lowest = [] {  // developer A/B only: CERB_PLANAR_LOWEST = the lowest level allowed on the planar path (read per call)
+        const char* e = cerb_dev_getenv("CERB_PLANAR_LOWEST");
+        return e ? atoi(e) : kPlanarLowest;
+    }();
     auto level_is_planar = [&](int u) {
-        if (dry || u < 2 || !net->planar || !net->fold_bn || net->conv_algo != 6 || net->head_algo < 1) return false;
-        const std::string n0 = "dec." + std::to_string(u) + ".0", n1 = "dec." + std::to_string(u) + ".1";
-        auto c0 = net->conv.find(n0), c1 = net->conv.find(n1);
-        if (c0 == net->conv.end() || c1 == net->conv.end() || !c0->second.wino) return false;
-        return (long long)hs[3 - u] * ws[3 - u] > 4096 && c0->second.cin == 64 && c0->second.cout == 64 && c1->second.cout == 64;
+        if (dry || !net->planar || !net->fold_bn || net->conv_algo != 6 || net->head_algo < 1) return false;
+        for (int v = 3; v >= u; --v) {
+            if (v < planar_lowest) return false;
+            auto c0 = net->conv.find("dec." + std::to_string(v) + ".0"), c1 = net->conv.find("dec." + std::to_string(v) + ".1");
+            if (c0 == net->conv.end() || c1 == net->conv.end() || !c0->second.wino || !c1->second.wino) return false;
+            const long long px = (long long)hs[3 - v] * ws[3 - v];
+            if ((hs[3 - v] & 3) || (ws[3 - v] & 3)) return false;  // whole 4 x 4 tiles (the lowest level of a 208-pixel tile is 26 x 26)
+            const bool ok = v >= 2 ? px >= 4096 && c0->second.cin == 64 && c0->second.cout == 64 && c1->second.cout == 64
+                                   : px >= 256 && c0->second.cin % 16 == 0 && c0->second.cout % 64 == 0 && c1->second.cin == c0->second.cout && c1->second.cout % 64 == 0;
+            if (!ok) return false;
+        }
+        return true;
     };
     if (!dry) {
         if (net->x0.ensure((size_t)N * H * W * 64 * 4, guard) || net->pool.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard)) return fail_alloc();
@@ -838,16 +864,23 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             // whole lines, nothing masks an edge.  Same arithmetic in the same order: bit-identical to the NHWC path (cerb_net_set_planar(0)).
             // The level below (same 64 channels at half the resolution) does the same when its maps are above conv_wino4b's range, and hands
             // its output to the last level's up-sampling in that layout.
-            const bool lvl_planar = level_is_planar(u) && (u == 3 || prev_gs > 0);
+            const bool lvl_planar = level_is_planar(u);
             if (lvl_planar) {
                 // two buffers per planar level: the entry sum is dead once the first conv has read it, so the second conv writes its output there
                 // (a third buffer of 8.6 GB at 64 tiles of 256^2 held it before); same geometry, same zero ring
-                PlanarBuf &bs = u == 3 ? net->psum : net->psum2, &bm = u == 3 ? net->pmid : net->pmid2, &bo = bs;
-                if (bs.ensure((int)D, N, hh, ww, 64, st) || bm.ensure((int)D, N, hh, ww, 64, st)) return fail_alloc();
-                if (prof_begin(net, n0 + ".up", "upsample2_add_planar", 0.0, st)) return 1;
+                PlanarBuf &bs = u == 3 ? net->psum : u == 2 ? net->psum2 : u == 1 ? net->psum1 : net->psum0;
+                PlanarBuf &bm = u == 3 ? net->pmid : u == 2 ? net->pmid2 : u == 1 ? net->pmid1 : net->pmid0;
+                // Below the two last levels the entry sum is wider than the level's output (256 -> 128, 128 -> 64 channels): another plane count moves
+                // every block, guard ring included, so an output written over the sum would leave the next call's ring dirty -- those levels keep a
+                // third buffer (a tenth of the last level's size), the 64 -> 64 levels reuse the sum buffer as before.
+                const int cout1 = net->conv[n1].cout;
+                PlanarBuf& bo = cout1 == cin0 ? bs : u == 1 ? net->pout1 : net->pout0;
+                if (bs.ensure((int)D, N, hh, ww, cin0, st) || bm.ensure((int)D, N, hh, ww, cmid, st) || (&bo != &bs && bo.ensure((int)D, N, hh, ww, cout1, st)))
+                    return fail_alloc();
+                if (prof_begin(net, n0 + ".up", kPlanarEntryFamily[u], 0.0, st)) return 1;
                 HIP_OK(cerb_launch_upsample2_add_planar(skips[u], prev, bs.b.p, (int)D, N, hh, ww, cin0, prev_gs, bs.gs(), use_roi ? roi_sum[u] : nullptr, prev_planar ? 1 : 0, st));
                 if (prof_end(net, st)) return 1;
-                net->planar_half = (u != 3);
+                net->planar_level = u;
                 if (run_conv(net, n0, bs.b.p, nullptr, nullptr, bm.b.p, N, hh, ww, 1, 0, bs.gs(), 0, st, macs, use_roi ? roi_mid[u] : nullptr, bm.gs()))
                     return 1;
                 if (run_conv(net, n1, bm.b.p, nullptr, nullptr, bo.b.p, N, hh, ww, 1, 0, bm.gs(), 0, st, macs, use_roi ? roi_out[u] : nullptr, bo.gs()))

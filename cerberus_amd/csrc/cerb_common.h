@@ -43,7 +43,7 @@ struct ConvParams {
     long long in_gs, prev_gs, w_gs, bias_gs, resid_gs, out_gs;  // per-group strides in elements
     // conv_wino4p.hip only: `in` / `out` are tile-planar tensors (planar_elems below); blocks per image column / row incl. the guard ring
     int pl_byp, pl_bxp;
-    int level_tag;        // conv_wino4p.hip: 1 = last decoder level, 0 = the level below it -- picks the kernel SYMBOL only (profiler statistics per launch size)
+    int level_tag;        // conv_wino4p.hip: 1 = last decoder level, 0 = the level below it, 2 = the two lowest levels -- picks the kernel SYMBOL only (profiler statistics per launch size)
     // conv_wino4.hip / conv_wino4b.hip, training forward only: per 16 x 16 output block the (sum, sum of squares) of every output channel over the
     // block's pixels inside the image, [group][bn_bpg blocks][Cout][2] doubles -- the BatchNorm behind the convolution finalises its batch
     // statistics from these instead of reading the output again (train_kernels.hip: bn_finalize_kernel).  nullptr: not produced.

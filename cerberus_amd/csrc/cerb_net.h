@@ -294,10 +294,12 @@ struct cerb_net {
     DevBuf x0, pool, x[5], ta, tb, cm, dmid, dsum, dout[4];
     PlanarBuf psum, pmid, pout;  // the last decoder level's private tensors in the tile-planar layout (conv_wino4p.hip), cerb_net_set_planar; psum also
                                  // receives the level's OUTPUT (it is dead once the first conv has read it): pout / pout2 are never allocated any more
-    bool planar_half = false;       // set by the decoder loop around the half-resolution level's run_conv calls (names the kernel symbol)
+    int planar_level = 3;           // set by the decoder loop around a planar level's run_conv calls: the level (names the kernel symbol and the profile family)
     PlanarBuf psum2, pmid2, pout2;  // the same for the level below it (64 channels at half the resolution) when its maps are large enough
+    PlanarBuf psum1, pmid1, pout1, psum0, pmid0, pout0;  // ... and for the quarter- and eighth-resolution levels (128 / 256 input channels) where those run
+                                                         // tile-planar; their output has fewer planes than their entry sum, so it has a buffer of its own
     int packed_items = 1;        // cerb_net_set_packed_items: conv_wino4b.hip packs 16 consecutive tiles per item on maps that are not whole 16 x 16 blocks (28^2, 56^2)
-    int planar = 1;              // cerb_net_set_planar: 1 (default) = that level runs upsample2_add_planar -> conv_wino4p x2 -> heads reading planar features
+    int planar = 1;              // cerb_net_set_planar: 1 (default) = the planar levels (cerb_api.hip: level_is_planar) run upsample2_add_planar -> conv_wino4p x2 -> heads reading planar features
     // optional per-launch timing (HIP events on the caller's stream)
     bool profiling = false;
     int crop_roi = 1;   // cerb_net_set_crop_roi: decoders / heads only compute what the centre crop keeps (conv_algo 1)
@@ -327,7 +329,7 @@ struct cerb_net {
         for (void* p : dev_allocs) (void)hipFree(p);
         if (copy_tab) (void)hipFree(copy_tab);
         if (pack_tab) (void)hipFree(pack_tab);
-        x0.release(); pool.release(); ta.release(); tb.release(); cm.release(); dmid.release(); dsum.release(); psum.release(); pmid.release(); pout.release(); psum2.release(); pmid2.release(); pout2.release();
+        x0.release(); pool.release(); ta.release(); tb.release(); cm.release(); dmid.release(); dsum.release(); psum.release(); pmid.release(); pout.release(); psum2.release(); pmid2.release(); pout2.release(); psum1.release(); pmid1.release(); pout1.release(); psum0.release(); pmid0.release(); pout0.release();
         t_mean.release(); t_rstd.release(); t_ws.release(); t_hid.release(); t_gap.release(); t_pc1.release(); t_idn.release(); t_dil.release();
         for (auto& b : tape) b.release();
         for (auto& b : x) b.release();

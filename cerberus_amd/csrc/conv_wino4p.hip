@@ -178,8 +178,9 @@ struct Item {
 };
 }  // namespace
 
-// LEVEL only names the symbol: the launches of the last decoder level (<1>) and of the level below it (<0>, a quarter of the work each) show
-// up as two kernels in a profiler's per-symbol statistics instead of one average over two launch sizes.
+// LEVEL only names the symbol: the launches of the last decoder level (<1>), of the level below it (<0>, a quarter of the work each) and of the
+// two lowest levels (<2>: 8 and 16 chunks per item instead of 4) show up as separate kernels in a profiler's per-symbol statistics instead of
+// one average over several launch sizes.
 template <int LEVEL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_wino4p_kernel(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -650,9 +651,10 @@ hipError_t cerb_launch_wino4p(ConvParams p, hipStream_t st) {
     const long long nblk = wino4_block_grid(p);
     if (p.pl_byp != (p.Ho + BLK - 1) / BLK + 2 || p.pl_bxp != (p.Wo + BLK - 1) / BLK + 2) return hipErrorInvalidValue;
     const long long items = (long long)p.groups * ((nblk + 1) / 2) * (p.Cout / 64);
-    auto kern = p.level_tag ? conv_wino4p_kernel<1> : conv_wino4p_kernel<0>;
-    static bool attr_done[2][64] = {};
-    return wino4_launch(kern, attr_done[p.level_tag ? 1 : 0], items, LDS_BYTES + PROF_BYTES, p, st);
+    const int tag = p.level_tag == 2 ? 2 : p.level_tag ? 1 : 0;
+    auto kern = tag == 2 ? conv_wino4p_kernel<2> : tag ? conv_wino4p_kernel<1> : conv_wino4p_kernel<0>;
+    static bool attr_done[3][64] = {};
+    return wino4_launch(kern, attr_done[tag], items, LDS_BYTES + PROF_BYTES, p, st);
 }
 
 #ifdef P4_PROF

@@ -131,4 +131,17 @@ int cerb_dev_dilate2(const float* dy, float* d, long long n, int H, int W, int C
     return (int)cerb_launch_dilate2(dy, d, n, H, W, C, (hipStream_t)st);
 }
 
+// ---- forward decoder entry, NHWC and tile-planar (bound by tests/test_decoder_low_planar_gpu.py itself: the forward path's launchers are otherwise reached
+// through cerb_net_forward only).  `out` of the planar form is a tile-planar tensor (cerb_common.h) of cerb_devfwd_planar_elems floats per group --------
+long long cerb_devfwd_planar_elems(int N, int H, int W, int C) { return cerb_planar_elems(N, H, W, C); }
+int cerb_devfwd_upsample2_add(const float* skip, const float* prev, float* out, int G, int N, int H, int W, int C, long long prev_gs, void* st) {
+    DEV_NEED(skip && prev && out && G > 0 && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0);
+    return (int)cerb_launch_upsample2_add(skip, prev, out, G, N, H, W, C, prev_gs, nullptr, (hipStream_t)st);
+}
+int cerb_devfwd_upsample2_add_planar(const float* skip, const float* prev, float* out, int G, int N, int H, int W, int C, long long prev_gs, long long out_gs,
+                                     int prev_planar, void* st) {
+    DEV_NEED(skip && prev && out && G > 0 && N > 0 && H > 0 && W > 0 && out_gs >= cerb_planar_elems(N, H, W, C));
+    return (int)cerb_launch_upsample2_add_planar(skip, prev, out, G, N, H, W, C, prev_gs, out_gs, nullptr, prev_planar, (hipStream_t)st);
+}
+
 }  // extern "C"

@@ -288,15 +288,19 @@ hipError_t cerb_launch_upsample2_add(const float* skip, const float* prev, float
 // wave, 4x4 tile m, channel quad) keeps the tile's 16 skip quads and the 4 x 4 source pixels of `prev` its 16 outputs blend, and every
 // store instruction of a wave is one contiguous 1-KiB row (pixel position (i, j) of the 16 tiles).  Same expressions, same order as
 // upsample2_add_kernel: the values are bit-identical.  Pixels of edge blocks beyond the image are not written (they stay zero).
-template <bool PREV_PLANAR>  // `prev` (half resolution) is NHWC, or tile-planar itself (the level below also runs on conv_wino4p.hip)
+// C = 64, 128 or 256 channels (the decoder's four levels): the workgroup's four waves serve four 16-channel planes of a block per pass and walk
+// the block's C / 16 planes in C / 64 passes.
+template <bool PREV_PLANAR, int C>  // `prev` (half resolution) is NHWC, or tile-planar itself (the level below also runs on conv_wino4p.hip)
 __global__ __launch_bounds__(256) void upsample2_add_planar_kernel(const float* __restrict__ skip, const float* __restrict__ prev, float* __restrict__ out,
                                                                    int groups, int N, int H, int W, long long prev_gs, long long out_gs, int byp, int bxp,
                                                                    int by_lo, int by_cnt, int bx_lo, int bx_cnt) {
-    constexpr int C = 64, NCC = 4;
+    static_assert(C % 64 == 0, "four 16-channel planes per pass");
+    constexpr int NCC = C / 16, NPASS = NCC / 4;
     const int Hp = H >> 1, Wp = W >> 1;
-    const int lane = threadIdx.x & 63, cc = threadIdx.x >> 6, m = lane >> 2, cq = lane & 3, ty = m >> 2, tx = m & 3;
-    const int nblk = N * by_cnt * bx_cnt;
-    for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int lane = threadIdx.x & 63, m = lane >> 2, cq = lane & 3, ty = m >> 2, tx = m & 3;
+    const int nwork = N * by_cnt * bx_cnt * NPASS;
+    for (int wk = blockIdx.x; wk < nwork; wk += gridDim.x) {
+        const int blk = wk / NPASS, cc = (wk % NPASS) * 4 + (int)(threadIdx.x >> 6);
         const int bx = blk % bx_cnt + bx_lo;
         const int r_ = blk / bx_cnt;
         const int by = r_ % by_cnt + by_lo, n = r_ / by_cnt;
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(256) void upsample2_add_planar_kernel(const float* 
 // roi = {y0, y1, x0, x1} in output pixels (nullptr or empty = the whole map): the 16 x 16 blocks overlapping it are written whole
 hipError_t cerb_launch_upsample2_add_planar(const float* skip, const float* prev, float* out, int groups, int N, int H, int W, int C, long long prev_gs,
                                             long long out_gs, const int* roi, int prev_planar, hipStream_t st) {
-    if (C != 64 || (H & 3) || (W & 3)) return hipErrorInvalidValue;
+    if ((C != 64 && C != 128 && C != 256) || (H & 3) || (W & 3)) return hipErrorInvalidValue;
     int by_lo = 0, by_hi = (H + 15) / 16, bx_lo = 0, bx_hi = (W + 15) / 16;
     if (roi && roi[1] > roi[0] && roi[3] > roi[2]) {
         by_lo = roi[0] / 16; by_hi = (roi[1] + 15) / 16;
@@ -377,8 +381,12 @@ hipError_t cerb_launch_upsample2_add_planar(const float* skip, const float* prev
 #ifndef UPP_GRID
 #define UPP_GRID 16
 #endif
-    long long blocks = nblk < 256 * UPP_GRID ? nblk : 256 * UPP_GRID;
-    auto kern = prev_planar ? upsample2_add_planar_kernel<true> : upsample2_add_planar_kernel<false>;
+    const long long nwork = nblk * (C / 64);  // one pass of a block = four planes = one workgroup's turn
+    if (nwork >= (1ll << 31)) return hipErrorInvalidValue;
+    long long blocks = nwork < 256 * UPP_GRID ? nwork : 256 * UPP_GRID;
+    auto kern = C == 64    ? (prev_planar ? upsample2_add_planar_kernel<true, 64> : upsample2_add_planar_kernel<false, 64>)
+                : C == 128 ? (prev_planar ? upsample2_add_planar_kernel<true, 128> : upsample2_add_planar_kernel<false, 128>)
+                           : (prev_planar ? upsample2_add_planar_kernel<true, 256> : upsample2_add_planar_kernel<false, 256>);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, skip, prev, out, groups, N, H, W, prev_gs, out_gs,
                        cerb_planar_blocks(H), cerb_planar_blocks(W), by_lo, by_hi - by_lo, bx_lo, bx_hi - bx_lo);
     return hipGetLastError();

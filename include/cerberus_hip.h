@@ -102,12 +102,13 @@ int cerb_net_forward(cerb_net* net, const cerb_forward_io* io, void* hip_stream)
  * outside the product library.)
  * The training step follows the same rule for its forward and data-gradient convolutions (filter transform on the device). */
 int cerb_net_set_conv_algo(cerb_net* net, int algo);
-/* Layout of the private tensors (skip + upsample, first conv output, level output / head features; models/net_desc.py:182-198) of the LAST
- * decoder level and of the level below it (both 64 channels; a level takes part when its maps are above 64 x 64 pixels):
+/* Layout of the private tensors (skip + upsample, first conv output, level output / head features; models/net_desc.py:182-198) of the
+ * decoder levels: the last level and the level below it (both 64 channels; a level takes part when its maps are at least 64 x 64 pixels) and,
+ * when both do, the two lowest levels (maps of at least one 16 x 16 block with sides that are multiples of 4; a level only if the one above it):
  *   1 (default) = tile-planar (cerb_common.h: cerb_planar_offset) through upsample2_add_planar -> conv_wino4p.hip x2 -> heads: a Winograd
  *                 wave's stores are contiguous 1-KiB rows and its patch loads whole lines, zero padding is data;
- *   0           = NHWC through conv_wino4.hip (round 2's path).
- * Same arithmetic in the same order: the outputs are bit-identical (tests/test_net_gpu.py).  Applies with conv_algo 6 and head_algo 1. */
+ *   0           = NHWC through conv_wino4.hip / conv_wino4b.hip (round 2's path).
+ * Same arithmetic in the same order: the outputs are bit-identical (tests/test_net_gpu.py, tests/test_decoder_low_planar_gpu.py).  Applies with conv_algo 6 and head_algo 1. */
 int cerb_net_set_planar(cerb_net* net, int enable);
 /* Work items of the F(4x4,3x3) kernel for maps up to 64 x 64 pixels (conv_wino4b.hip) on maps whose sides are multiples of 4 but not of 16 -- the
  * 28 x 28 / 56 x 56 maps of the reference's default 448-pixel patch (infer/tile.py:43-106, models/backbone/resnet.py:273-286), in inference and in
