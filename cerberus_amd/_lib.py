@@ -16,6 +16,7 @@ EXPORTS = [
     "cerb_valid_stats_bytes", "cerb_valid_stats_reset", "cerb_valid_stats_accumulate",
     "cerb_jpeg_workspace_bytes", "cerb_jpeg_decode_stream", "cerb_jpeg_read_tiles", "cerb_jpeg_decode_window",
     "cerb_tissue_workspace_bytes", "cerb_tissue_hed", "cerb_tissue_entropy", "cerb_tissue_histogram", "cerb_tissue_threshold", "cerb_tissue_morphology",
+    "cerb_inst_areas", "cerb_inst_pairs_workspace_bytes", "cerb_inst_pairs", "cerb_inst_pairs_compact", "cerb_inst_pair_stats_workspace_bytes", "cerb_inst_pair_stats",
 ]
 
 
@@ -196,6 +197,16 @@ def lib():
     L.cerb_tissue_histogram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cerb_tissue_threshold.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
     L.cerb_tissue_morphology.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.cerb_inst_areas.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_inst_pairs_workspace_bytes.argtypes = [C.c_longlong]
+    L.cerb_inst_pairs_workspace_bytes.restype = C.c_size_t
+    L.cerb_inst_pairs.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_longlong, C.c_void_p]
+    L.cerb_inst_pairs_compact.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.cerb_inst_pair_stats_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.cerb_inst_pair_stats_workspace_bytes.restype = C.c_size_t
+    L.cerb_inst_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

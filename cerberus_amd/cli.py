@@ -58,6 +58,16 @@ WSI_MODEL_OPTIONS = [
                                     "streaming are refused"),
 ]
 WSI_ALL_OPTIONS = WSI_OPTIONS + WSI_MODEL_OPTIONS
+# compute_stats.py (not a driver of the reference's command line: its compute_stats.py is a script with paths edited in place)
+STATS_OPTIONS = [
+    ("--gpu", True, "0", "GPU id, exported as HIP_VISIBLE_DEVICES"),
+    ("--pred_dir", True, None, "the --output_dir of run_infer_tile.py: <pred_dir>/<tissue>_mat/<name>.mat are read ('inst_map', and 'id' / 'type' with --types); "
+                               "stats.csv is written here"),
+    ("--true_dir", True, None, "directory of <name>.mat or <name>.npy annotations holding 'inst_map' and optionally 'inst_type' (one class per instance, in "
+                               "ascending id order)"),
+    ("--tissue", True, "nuclei", "which <tissue>_mat to score: nuclei | gland | lumen"),
+    ("--types", True, None, "number of classes, background included: also report PQ per class 1 .. n-1 and their mean (needs 'inst_type' on the true side)"),
+]
 
 
 def usage(prog, options):

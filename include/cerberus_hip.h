@@ -523,6 +523,45 @@ int cerb_jpeg_read_tiles(int fd, int n_tiles, const int64_t* offsets, const int6
 int cerb_jpeg_decode_window(const void* dev_buf, size_t dev_bytes, int n_tiles, int tile_w, int tile_h, uint8_t* scratch, size_t scratch_bytes,
                             uint8_t* dst, long long dst_row_stride, int x0, int y0, int x1, int y1, void* hip_stream);
 
+/* ---- instance metrics between two label maps: contingency table, PQ / AJI / Dice2 / Dice1 counters (cerberus_amd/inst_metrics.py) ------------------
+ * Maps are int32 with a row stride in elements (every pixel offset is 64-bit: a view whose last row lies past 2^31 elements is fine); 0 is background
+ * and an id outside [1, n_ids] -- negative, or above the bound the caller states -- counts as background too (as in cerb_relabel) and never indexes a
+ * table.  Nothing outside h x w is read.  All calls queue on hip_stream, allocate nothing and do not synchronise.
+ *   cerb_inst_areas        area[id] += pixels of id, for ids in [1, n_ids]; area: int64 [n_ids + 1], cleared by the caller (area[0] is not written).
+ *   cerb_inst_pairs        the sparse table of pixel counts per (true id, pred id) with both > 0.  true_index / pred_index: int32 [n_ids + 1], the
+ *                          1-based rank of every id that occurs among the ids that occur, 0 for one that does not (area > 0, exclusive scan); a
+ *                          pair's key is (true rank << 32) | pred rank.  table: cerb_inst_pairs_workspace_bytes(capacity) bytes, 8-byte aligned,
+ *                          capacity a power of two; the call clears it.  It starts with four int64 words {n_pairs, overflow, updates kept on chip,
+ *                          updates sent to the table}, then keys[capacity] (0 = free) and counts[capacity].  Probing is bounded: when a key finds
+ *                          no slot the update is DROPPED and overflow becomes 1 -- the result is then unusable and the caller repeats the call with a
+ *                          larger capacity (4 x is what the Python side does).  Slots are taken modulo capacity: no overflow writes out of bounds.
+ *   cerb_inst_pairs_compact  the occupied slots as keys_out / counts_out (int64, up to max_out entries, in no particular order -- sort by key);
+ *                          *n_out (device int64, cleared by the call) = number of occupied slots.
+ *   cerb_inst_pair_stats   from the pairs SORTED by key, the areas by rank (true_area[rank - 1]) and optional per-instance classes by rank:
+ *                          summary (device int64 [CERB_INST_SUMMARY_WORDS]) = {tp, fp, fn, aji_inter, aji_union, dice2_inter, dice2_total,
+ *                          dice1_inter, dice1_total, n_true, n_pred, 0} and *sum_iou (device double).  cls >= 0 keeps only the true and pred
+ *                          instances of that class (both type vectors required) -- the same numbers as on maps with the other instances zeroed;
+ *                          cls < 0: no filter.  ws: cerb_inst_pair_stats_workspace_bytes(n_true, n_pred) bytes, 8-byte aligned.
+ * Rules, with a, b the areas, c > 0 a pair's count, u = a + b - c:
+ *   a pair matches iff 2 c > u (IoU > 0.5; matches are unique); tp = matches, fn = n_true - tp, fp = n_pred - tp, sum_iou = sum of c / u over them.
+ *   AJI: per true instance with a pair, the pred p* of largest c / u (compared as c1 u2 > c2 u1 in 128 bits; a tie goes to the smaller pred id):
+ *   aji_inter += c, aji_union += u, p* is used; a true instance without a pair adds a to aji_union, every pred never used adds b.
+ *   dice2_inter = sum c over the pairs, dice2_total = sum (a + b) over the pairs; dice1_inter = sum c, dice1_total = sum a + sum b over the instances.
+ * Every decision is integer arithmetic.  sum_iou is float64, each term the correctly rounded c / u, added in one fixed order: two runs agree bitwise.
+ * The ratios (dq, sq, pq, aji, dice2, dice1) are host arithmetic on these numbers (cerberus_amd/inst_metrics.py). */
+#define CERB_INST_SUMMARY_WORDS 12
+int cerb_inst_areas(const int32_t* labels, long long row_stride, int h, int w, int n_ids, long long* area, void* hip_stream);
+size_t cerb_inst_pairs_workspace_bytes(long long capacity);
+int cerb_inst_pairs(const int32_t* true_map, long long true_row_stride, const int32_t* pred_map, long long pred_row_stride, int h, int w,
+                    const int32_t* true_index, int n_true_ids, const int32_t* pred_index, int n_pred_ids, void* table, long long capacity,
+                    void* hip_stream);
+int cerb_inst_pairs_compact(const void* table, long long capacity, long long* keys_out, long long* counts_out, long long max_out,
+                            long long* n_out, void* hip_stream);
+size_t cerb_inst_pair_stats_workspace_bytes(int n_true, int n_pred);
+int cerb_inst_pair_stats(const long long* keys, const long long* counts, long long n_pairs, const long long* true_area, int n_true,
+                         const long long* pred_area, int n_pred, const int32_t* true_type, const int32_t* pred_type, int cls,
+                         long long* summary, double* sum_iou, void* ws, size_t ws_bytes, void* hip_stream);
+
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
 int cerb_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms); /* synchronises on ev_stop */
