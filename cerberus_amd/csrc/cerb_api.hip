@@ -234,6 +234,10 @@ static void pack_wino4(const float* w, int cout, int cin, std::vector<float>* ou
                         }
 }
 
+// the host packers by themselves (dev_entry.hip: kernel-level tests launch one convolution on weights they bring)
+void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, std::vector<float>* out) { pack_conv(w, nullptr, cout, cin, ks, chunk, out); }
+void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out) { pack_wino4(w, cout, cin, out, layout); }
+
 static int store_bn(cerb_net* net, const std::string& name, const std::vector<std::string>& bnkeys, int ch) {
     std::vector<float> ga, be;
     for (const std::string& k : bnkeys) {
@@ -568,11 +572,19 @@ int train_wino4_slot(cerb_net* net, const std::string& name, PackedConv& cm, int
 
 // The lowest decoder level that runs tile-planar when everything above it does (level_is_planar in forward_impl; 2 = the two last levels only).
 static constexpr int kPlanarLowest = 0;
+// The encoder's residual stages (bit li = backbone.layer<li + 1>) that run tile-planar where their geometry allows it (encoder_stage_is_planar in
+// forward_impl): decided per stage by measurement on the headline's batch (32 tiles of 256^2; profiles/encoder_planar_ab.txt), entry and exit passes
+// included.  Stages 1..3 (128^2 x 64, 64^2 x 128, 32^2 x 256) win in every round; stage 4 (16^2 x 512: one block per image, so 16 block pairs x 8 blocks of
+// 64 output channels = 128 items for 256 workgroups, where conv_wino4b's one-block items fill them) loses 0.33 ms and stays on NHWC.
+static constexpr int kEncPlanarStages = 0x7;
 // Profile families of the tile-planar launches, by decoder level (bench.py's table keeps the levels apart).  The two lowest levels' names start with
 // "conv_wino4_planar", not "conv_wino4p": tests/test_net_gpu.py counts the families that start with "conv_wino4p" (and the entry passes named exactly
 // "upsample2_add_planar") and expects the two last levels' four (two) launches.
 static const char* const kPlanarFamily[4] = {"conv_wino4_planar<f4x4,16x16x2,eighth-res>", "conv_wino4_planar<f4x4,16x16x2,quarter-res>",
                                              "conv_wino4p<f4x4,16x16x2,planar,half-res>", "conv_wino4p<f4x4,16x16x2,planar>"};
+// The encoder's planar stages: the names start with "conv_wino4" (bench.py prices executed FLOPs by that prefix) and with none of the decoder's prefixes.
+static const char* const kEncPlanarFamily = "conv_wino4_enc<f4x4,16x16x2>";
+static const char* const kEncPlanarFamilyRes = "conv_wino4_enc<f4x4,16x16x2,res>";
 static const char* const kPlanarEntryFamily[4] = {"upsample2_add_planar<eighth-res>", "upsample2_add_planar<quarter-res>", "upsample2_add_planar", "upsample2_add_planar"};
 
 int run_conv(cerb_net* net, const std::string& name, const float* in, const float* prev, const float* resid, float* out, int N,
@@ -619,7 +631,19 @@ int run_conv(cerb_net* net, const std::string& name, const float* in, const floa
         return e ? atoll(e) : 4096ll;
     }();
     const bool w4b = !planar && (net->conv_algo == 7 || (net->conv_algo == 6 && map_px <= w4b_max_px)) && c.cin % 64 == 0;
-    if (planar && !(use_w4 && c.wino && mode == 0 && net->fold_bn && !resid)) return fail("internal: conv " + name + " cannot take the planar path");
+    const bool enc_planar = planar && net->planar_level == 4;  // an encoder stage: the only planar launches with a residual, and with stride-2 producers
+    if (enc_planar && c.stride == 2) {  // the stage's entry: NHWC in, tile-planar out (conv_igemm.hip)
+        if (resid || mode != 0 || !net->fold_bn) return fail("internal: conv " + name + " cannot store tile-planar");
+        p.out_gs = planar_out_gs;
+        p.pl_byp = cerb_planar_blocks(p.Ho);
+        p.pl_bxp = cerb_planar_blocks(p.Wo);
+        const std::string kn = "conv_igemm_planar<ks" + std::to_string(c.ks) + ",s2" + (p.Wo < 32 ? ",16x16>" : ",8x32>");
+        if (prof_begin(net, name, kn, fl, st)) return 1;
+        HIP_OK(cerb_launch_conv(p, c.ks, c.stride, mode, st));
+        if (prof_end(net, st)) return 1;
+        return 0;
+    }
+    if (planar && !(use_w4 && c.wino && mode == 0 && net->fold_bn && (!resid || enc_planar))) return fail("internal: conv " + name + " cannot take the planar path");
     if (use_w4 && c.wino && mode == 0 && (!it->second.host_w.empty() || !net->fold_bn)) {
         PackedConv& cm = it->second;
         float* train_slot = nullptr;
@@ -645,11 +669,11 @@ int run_conv(cerb_net* net, const std::string& name, const float* in, const floa
         }
         if (planar) {
             p.out_gs = planar_out_gs;
-            p.level_tag = net->planar_level == 3 ? 1 : net->planar_level == 2 ? 0 : 2;
+            p.level_tag = enc_planar ? (resid ? 4 : 3) : net->planar_level == 3 ? 1 : net->planar_level == 2 ? 0 : 2;
             p.pl_byp = cerb_planar_blocks(p.Ho);
             p.pl_bxp = cerb_planar_blocks(p.Wo);
         }
-        if (prof_begin(net, name, planar ? kPlanarFamily[net->planar_level & 3] : w4b ? (cerb_wino4b_packed(p) ? (resid ? "conv_wino4b<f4x4,16t,res>" : "conv_wino4b<f4x4,16t>") : (resid ? "conv_wino4b<f4x4,16x16,res>" : "conv_wino4b<f4x4,16x16>")) : (resid ? "conv_wino4<f4x4,16x16x2,res>" : "conv_wino4<f4x4,16x16x2>"), fl_done, st)) return 1;
+        if (prof_begin(net, name, enc_planar ? (resid ? kEncPlanarFamilyRes : kEncPlanarFamily) : planar ? kPlanarFamily[net->planar_level & 3] : w4b ? (cerb_wino4b_packed(p) ? (resid ? "conv_wino4b<f4x4,16t,res>" : "conv_wino4b<f4x4,16t>") : (resid ? "conv_wino4b<f4x4,16x16,res>" : "conv_wino4b<f4x4,16x16>")) : (resid ? "conv_wino4<f4x4,16x16x2,res>" : "conv_wino4<f4x4,16x16x2>"), fl_done, st)) return 1;
         if (net->conv_bn_part && !planar && !resid && !(roi && roi[1] > roi[0] && roi[3] > roi[2])) {
             p.bn_part = net->conv_bn_part;
             net->conv_bn_bpg = w4b ? cerb_wino4b_bn_blocks(p) : N * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
@@ -759,15 +783,72 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
         if (prof_begin(net, "stem", "stem_conv7x7", 2.0 * N * H * W * 64.0 * 147.0, st)) return 1;
         HIP_OK(cerb_launch_stem(sp, st));
         if (prof_end(net, st)) return 1;
-        if (prof_begin(net, "maxpool", "maxpool3x3s2", 0.0, st)) return 1;
-        HIP_OK(cerb_launch_maxpool(net->x0.p, net->pool.p, N, H, W, 64, st));
-        if (prof_end(net, st)) return 1;
+    }
+    // Which residual stages keep conv1's output, conv2's output and the block identity in the tile-planar layout and run their stride-1 3x3 convolutions
+    // on conv_wino4p.hip (two blocks per weight register): inference on the default algorithms with folded BatchNorm only.  Decided
+    // from the stage's geometry alone -- never from the batch size or cerb_net_set_packed_items -- so that a tile's values do not depend on what it is
+    // batched with: the map's sides are multiples of 16 (whole blocks: the 56^2 and 28^2 maps of a 448-pixel patch stay on conv_wino4b's packed items),
+    // its channels a multiple of 64, every stride-1 convolution Winograd-packed.  Same arithmetic in the same order as the NHWC kernels: bit-identical.
+    const int enc_mask = [] {  // developer A/B only: CERB_ENC_PLANAR = bit mask of the stages 1..4 allowed on the planar path (read per call)
+        const char* e = cerb_dev_getenv("CERB_ENC_PLANAR");
+        return e ? atoi(e) : kEncPlanarStages;
+    }();
+    auto encoder_stage_is_planar = [&](int li) {
+        if (dry || !net->planar || !net->fold_bn || net->conv_algo != 6 || !((enc_mask >> li) & 1)) return false;
+        const int hh = hs[li + 1], ww = ws[li + 1], planes = kFilters[li + 1];
+        if ((hh & 15) || (ww & 15) || hh < 16 || ww < 16 || planes % 64) return false;
+        for (int b = 0; b < kLayers[li]; ++b)
+            for (int j = 1; j <= 2; ++j) {
+                auto c = net->conv.find("backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b) + ".conv" + std::to_string(j));
+                if (c == net->conv.end()) return false;
+                if (c->second.stride == 1 && (!c->second.wino || c->second.host_w.empty() || c->second.cin % 16)) return false;
+            }
+        return true;
+    };
+    if (!dry) {
+        if (encoder_stage_is_planar(0)) {
+            if (net->enc_a[0].ensure(1, N, hs[1], ws[1], 64, st)) return fail_alloc();
+            if (prof_begin(net, "maxpool", "maxpool3x3s2_planar", 0.0, st)) return 1;
+            HIP_OK(cerb_launch_maxpool_planar(net->x0.p, net->enc_a[0].b.p, N, H, W, 64, st));
+            if (prof_end(net, st)) return 1;
+        } else {
+            if (prof_begin(net, "maxpool", "maxpool3x3s2", 0.0, st)) return 1;
+            HIP_OK(cerb_launch_maxpool(net->x0.p, net->pool.p, N, H, W, 64, st));
+            if (prof_end(net, st)) return 1;
+        }
     }
     float* cur = dry ? nullptr : net->pool.p;
     int inpl = 64;
     for (int li = 0; li < 4; ++li) {
         const int planes = kFilters[li + 1];
         const int Hi = (li == 0) ? hs[1] : hs[li], Wi = (li == 0) ? ws[1] : ws[li];  // input resolution of this layer
+        if (encoder_stage_is_planar(li)) {
+            // conv1 -> B, conv2(B) + identity(A) -> A in place (conv_wino4p.hip: every element of the residual is read by the lane that writes it); block 0
+            // of the stages 2..4 fills B and A from the NHWC input through the stride-2 convolutions' planar epilogue, stage 1's A is the pooled map
+            PlanarBuf &ba = net->enc_a[li], &bb = net->enc_b[li];
+            const int hh = hs[li + 1], ww = ws[li + 1];
+            if (ba.ensure(1, N, hh, ww, planes, st) || bb.ensure(1, N, hh, ww, planes, st)) return fail_alloc();
+            const int keep_level = net->planar_level;
+            net->planar_level = 4;
+            struct Restore { cerb_net* n; int v; ~Restore() { n->planar_level = v; } } restore{net, keep_level};
+            for (int b = 0; b < kLayers[li]; ++b) {
+                const std::string p = "backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b);
+                if (b == 0 && li > 0) {
+                    if (run_conv(net, p + ".conv1", cur, nullptr, nullptr, bb.b.p, N, Hi, Wi, 1, 0, 0, 0, st, macs, nullptr, bb.gs())) return 1;
+                    if (run_conv(net, p + ".downsample", cur, nullptr, nullptr, ba.b.p, N, Hi, Wi, 0, 0, 0, 0, st, macs, nullptr, ba.gs())) return 1;
+                } else if (run_conv(net, p + ".conv1", ba.b.p, nullptr, nullptr, bb.b.p, N, hh, ww, 1, 0, ba.gs(), 0, st, macs, nullptr, bb.gs())) {
+                    return 1;
+                }
+                if (run_conv(net, p + ".conv2", bb.b.p, nullptr, ba.b.p, ba.b.p, N, hh, ww, 1, 0, bb.gs(), 0, st, macs, nullptr, ba.gs())) return 1;
+            }
+            // the stage's exit: its consumers (the next stage's stride-2 convolutions, conv_map, Patch-Class, the decoder's skips, io->feats) read NHWC
+            if (prof_begin(net, "backbone.layer" + std::to_string(li + 1) + ".exit", "planar_to_nhwc", 0.0, st)) return 1;
+            HIP_OK(cerb_launch_planar_to_nhwc(ba.b.p, net->x[li + 1].p, N, hh, ww, planes, st));
+            if (prof_end(net, st)) return 1;
+            cur = net->x[li + 1].p;
+            inpl = planes;
+            continue;
+        }
         for (int b = 0; b < kLayers[li]; ++b) {
             const std::string p = "backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b);
             const int stride = (b == 0 && li > 0) ? 2 : 1;

@@ -113,6 +113,8 @@ hipError_t cerb_launch_head_bwd2(const float* hid, const float* dlog, const floa
                                  const float* dgamma, const float* dbeta, const float* w1, const float* w2, float* dprev, float* dw1, float* db1, long long rows, int out,
                                  int eval_mode, int assign, void* ws, hipStream_t st, const float* const* in_bn = nullptr, double* in_part = nullptr);
 hipError_t cerb_launch_maxpool(const float* in, float* out, int N, int H, int W, int C, hipStream_t st);
+hipError_t cerb_launch_maxpool_planar(const float* in, float* out, int N, int H, int W, int C, hipStream_t st);  // `out` tile-planar (pooled map: multiples of 16, C % 64 == 0)
+hipError_t cerb_launch_planar_to_nhwc(const float* in, float* out, int N, int H, int W, int C, hipStream_t st);  // tile-planar [N][H][W][C] -> NHWC (H, W multiples of 16, C % 64 == 0)
 hipError_t cerb_launch_head(const HeadParams& p, hipStream_t st);
 hipError_t cerb_launch_head_group(const HeadParams* heads, int n_heads, hipStream_t st, int w2_44);
 struct PatchClassParams {
@@ -294,10 +296,14 @@ struct cerb_net {
     DevBuf x0, pool, x[5], ta, tb, cm, dmid, dsum, dout[4];
     PlanarBuf psum, pmid, pout;  // the last decoder level's private tensors in the tile-planar layout (conv_wino4p.hip), cerb_net_set_planar; psum also
                                  // receives the level's OUTPUT (it is dead once the first conv has read it): pout / pout2 are never allocated any more
-    int planar_level = 3;           // set by the decoder loop around a planar level's run_conv calls: the level (names the kernel symbol and the profile family)
+    int planar_level = 3;           // set by the decoder loop around a planar level's run_conv calls: the level (names the kernel symbol and the profile family);
+                                    // 4 = an encoder stage (conv_wino4_enc<...>)
     PlanarBuf psum2, pmid2, pout2;  // the same for the level below it (64 channels at half the resolution) when its maps are large enough
     PlanarBuf psum1, pmid1, pout1, psum0, pmid0, pout0;  // ... and for the quarter- and eighth-resolution levels (128 / 256 input channels) where those run
                                                          // tile-planar; their output has fewer planes than their entry sum, so it has a buffer of its own
+    // The encoder's residual stages that run tile-planar (cerb_api.hip: encoder_stage_is_planar), per stage: enc_a = the block's identity and, written over
+    // it, the block's output; enc_b = the first convolution's output.
+    PlanarBuf enc_a[4], enc_b[4];
     int packed_items = 1;        // cerb_net_set_packed_items: conv_wino4b.hip packs 16 consecutive tiles per item on maps that are not whole 16 x 16 blocks (28^2, 56^2)
     int planar = 1;              // cerb_net_set_planar: 1 (default) = the planar levels (cerb_api.hip: level_is_planar) run upsample2_add_planar -> conv_wino4p x2 -> heads reading planar features
     // optional per-launch timing (HIP events on the caller's stream)
@@ -331,6 +337,8 @@ struct cerb_net {
         if (pack_tab) (void)hipFree(pack_tab);
         x0.release(); pool.release(); ta.release(); tb.release(); cm.release(); dmid.release(); dsum.release(); psum.release(); pmid.release(); pout.release(); psum2.release(); pmid2.release(); pout2.release(); psum1.release(); pmid1.release(); pout1.release(); psum0.release(); pmid0.release(); pout0.release();
         t_mean.release(); t_rstd.release(); t_ws.release(); t_hid.release(); t_gap.release(); t_pc1.release(); t_idn.release(); t_dil.release();
+        for (auto& b : enc_a) b.release();
+        for (auto& b : enc_b) b.release();
         for (auto& b : tape) b.release();
         for (auto& b : x) b.release();
         for (auto& b : dout) b.release();
@@ -341,11 +349,14 @@ struct cerb_net {
 
 static const int kLayers[4] = {3, 4, 6, 3};            // ResNet34 (models/backbone/resnet.py:273-286)
 static const int kFilters[5] = {64, 64, 128, 256, 512};
+void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, std::vector<float>* out);   // [cout][cin][ks][ks] -> conv_igemm.hip's stream
+void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out);         // F(4x4,3x3) transform; layout 0 = conv_wino4 / 4p, 1 = conv_wino4b
 int prof_begin(cerb_net* net, const std::string& name, const std::string& kernel, double flops, hipStream_t st);  // per-launch records (cerb_net_profile_*)
 int prof_end(cerb_net* net, hipStream_t st);
 int train_wino2_fresh(cerb_net* net, const std::string& name, PackedConv& cm, int dgrad, hipStream_t st);
 int train_wino4_slot(cerb_net* net, const std::string& name, PackedConv& cm, int w4b, int dgrad, hipStream_t st, float** out);
 // one convolution of the schedule by its packed name (algorithm by cerb_net_set_conv_algo and the layer's geometry); planar_out_gs > 0: in / out are tile-planar
+// (a stride-2 convolution: `out` only -- conv_igemm.hip's planar epilogue)
 int run_conv(cerb_net* net, const std::string& name, const float* in, const float* prev, const float* resid, float* out, int N, int H, int W, int relu, int mode,
              long long in_gs, long long prev_gs, hipStream_t st, double* macs, const int* roi = nullptr, long long planar_out_gs = 0);
 #endif  // CERB_NET_H

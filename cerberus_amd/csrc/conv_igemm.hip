@@ -74,7 +74,10 @@ struct Item {
     int g, cb, n, oy0, ox0, tx, ty;
 };
 
-template <int KS, int STRIDE, int TH, int TW, int CB, int MODE>
+// PL: the output is a TILE-PLANAR tensor (cerb_common.h: cerb_planar_offset; the entry of an encoder stage that runs on conv_wino4p.hip).  A lane still
+// owns one pixel and four consecutive output channels per store: the planar address is a uniform item origin + a per-lane constant + an immediate,
+// so only the epilogue's address set-up differs -- the chunk body is the NHWC instantiation's.  Ho and Wo are multiples of 16, no residual.
+template <int KS, int STRIDE, int TH, int TW, int CB, int MODE, bool PL = false>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvParams p) {
     using C = ConvCfg<KS, STRIDE, TH, TW, CB, MODE>;
     constexpr int WD = C::WD;
@@ -187,7 +190,10 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvParams p) {
         const int pl = (wave * 2 + q) * 32 + j;
         const int py = pl / TW, px = pl % TW;
         ldsb[q] = ((py * C::LSTEP) * C::IW + px * C::LSTEP) * C::PS + 4 * h;
-        ooff[q] = (unsigned)(((py * p.Wo + px) * p.Cout + 4 * h) * 4);
+        if constexpr (PL)  // block column px >> 4 of the tile (8 x 32 tiles span two blocks), pixel position row (py & 3, px & 3), tile (py >> 2, (px >> 2) & 3)
+            ooff[q] = (unsigned)(((px >> 4) * (p.Cout >> 4) * 4096 + ((py & 3) * 4 + (px & 3)) * 256 + ((py >> 2) * 4 + ((px >> 2) & 3)) * 16 + 4 * h) * 4);
+        else
+            ooff[q] = (unsigned)(((py * p.Wo + px) * p.Cout + 4 * h) * 4);
     }
     float* aux = lds + C::MAIN_FLOATS;
     // MODE 1 bilinear invariants.  dst (gy, gx) = (oy0 - 1 + iy, ox0 - 1 + ix) with oy0, ox0 even: src0 = ((g - 1) >> 1) ->
@@ -396,7 +402,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvParams p) {
         // ---- epilogue: + bias (+ residual) -> ReLU -> float4 NHWC stores ------------------------------------------------
         {
             const float* bias = p.bias + w.g * p.bias_gs + w.cb * 64 + h * 4;
-            const long long origin = (((long long)w.n * p.Ho + w.oy0) * p.Wo + w.ox0) * p.Cout + w.cb * 64;  // floats, uniform
+            // floats, uniform; PL: the tile's first block (guard ring: + 1), the item's first plane, and for 8-row tiles the tile row inside the block
+            const long long origin = PL ? ((((long long)w.n * p.pl_byp + (w.oy0 >> 4) + 1) * p.pl_bxp + (w.ox0 >> 4) + 1) * (p.Cout >> 4) + w.cb * 4) * 4096 + ((w.oy0 >> 2) & 3) * 64
+                                        : (((long long)w.n * p.Ho + w.oy0) * p.Wo + w.ox0) * p.Cout + w.cb * 64;
             const __amdgpu_buffer_rsrc_t r_out = make_rsrc(p.out + w.g * p.out_gs + origin);
             const __amdgpu_buffer_rsrc_t r_res = make_rsrc(p.resid ? p.resid + w.g * p.resid_gs + origin : p.out);
             const bool has_res = p.resid != nullptr;
@@ -414,14 +422,14 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvParams p) {
                         const int co = s * 32 + rq * 8;  // cout quad (+ 4 h in the lane offsets)
                         f32x4 o = {acc[s][q][rq * 4 + 0], acc[s][q][rq * 4 + 1], acc[s][q][rq * 4 + 2], acc[s][q][rq * 4 + 3]};
                         o = o + *reinterpret_cast<const f32x4*>(bias + co);
-                        if (has_res) o = o + buf_load(r_res, ooff[q], co * 4);
+                        if (!PL && has_res) o = o + buf_load(r_res, ooff[q], co * 4);
                         if (p.relu) {
                             o[0] = fmaxf(o[0], 0.f);
                             o[1] = fmaxf(o[1], 0.f);
                             o[2] = fmaxf(o[2], 0.f);
                             o[3] = fmaxf(o[3], 0.f);
                         }
-                        buf_store(o, r_out, ooff[q], co * 4);
+                        buf_store(o, r_out, ooff[q], PL ? (co >> 4) * 16384 + (co & 15) * 4 : co * 4);
                     }
                 }
             }
@@ -436,13 +444,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvParams p) {
 // ------------------------------------------------------------------------------------------------
 // Host-side launcher (called from cerb_api.hip)
 // ------------------------------------------------------------------------------------------------
-template <int KS, int STRIDE, int TH, int TW, int CB, int MODE>
+template <int KS, int STRIDE, int TH, int TW, int CB, int MODE, bool PL = false>
 static hipError_t launch_cfg(ConvParams p, hipStream_t st) {
     using C = ConvCfg<KS, STRIDE, TH, TW, CB, MODE>;
     p.tiles_x = (p.Wo + TW - 1) / TW;
     p.tiles_y = (p.Ho + TH - 1) / TH;
     const long long items = (long long)p.groups * p.N * p.tiles_x * p.tiles_y * (p.Cout / 64);
-    auto kern = conv_igemm_kernel<KS, STRIDE, TH, TW, CB, MODE>;
+    auto kern = conv_igemm_kernel<KS, STRIDE, TH, TW, CB, MODE, PL>;
     static bool attr_done[64] = {};
     if (cerb_attr_needed(attr_done)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
@@ -467,6 +475,14 @@ extern "C" size_t cerb_conv_guard_bytes(int tile_w) { return (size_t)17 * (size_
 
 hipError_t cerb_launch_conv(const ConvParams& p, int ks, int stride, int mode, hipStream_t st) {
     const bool small = p.Wo < 32;  // 16x16 tiles for the deepest levels (16^2 / 28^2 maps)
+    if (p.pl_byp > 0) {  // tile-planar output: the two stride-2 convolutions at the entry of an encoder stage
+        if (stride != 2 || mode != 0 || p.resid || (p.Ho & 15) || (p.Wo & 15) || p.Ho < 16 || p.Wo < 16 || p.groups != 1 || p.pl_byp != cerb_planar_blocks(p.Ho) ||
+            p.pl_bxp != cerb_planar_blocks(p.Wo))
+            return hipErrorInvalidValue;
+        if (ks == 3) return small ? launch_cfg<3, 2, 16, 16, 16, 0, true>(p, st) : launch_cfg<3, 2, 8, 32, 16, 0, true>(p, st);
+        if (ks == 1) return small ? launch_cfg<1, 2, 16, 16, 16, 0, true>(p, st) : launch_cfg<1, 2, 8, 32, 16, 0, true>(p, st);
+        return hipErrorInvalidValue;
+    }
     if (ks == 3 && stride == 1 && mode == 0) return small ? launch_cfg<3, 1, 16, 16, 32, 0>(p, st) : launch_cfg<3, 1, 8, 32, 32, 0>(p, st);
     if (ks == 3 && stride == 1 && mode == 1) return small ? launch_cfg<3, 1, 16, 16, 32, 1>(p, st) : launch_cfg<3, 1, 8, 32, 32, 1>(p, st);
     if (ks == 3 && stride == 2 && mode == 0) return small ? launch_cfg<3, 2, 16, 16, 16, 0>(p, st) : launch_cfg<3, 2, 8, 32, 16, 0>(p, st);

@@ -180,10 +180,12 @@ struct Item {
 
 // LEVEL only names the symbol: the launches of the last decoder level (<1>), of the level below it (<0>, a quarter of the work each) and of the
 // two lowest levels (<2>: 8 and 16 chunks per item instead of 4) show up as separate kernels in a profiler's per-symbol statistics instead of
-// one average over several launch sizes.
+// one average over several launch sizes.  <3> and <4> are the encoder's residual stages (cerb_api.hip: encoder_stage_is_planar): <4> adds a
+// tile-planar residual (the BasicBlock's identity) between the output transform and the ReLU floor, <3> is the block's first convolution.
 template <int LEVEL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_wino4p_kernel(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool RES = LEVEL == 4;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int a = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's 16 output channels of the item's 64 (= one output plane); input path: block a >> 1
@@ -583,6 +585,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 const long long origin = p.out_gs * w.g + ((((long long)bo.n * p.pl_byp + by_abs + 1) * p.pl_bxp + bx_abs + 1) * nplane_o + w.cb * 4 + a) * (long long)(PLANE_BYTES / 4);
                 const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(p.out + origin, 0, PLANE_BYTES, 0x00020000);
                 const bool partial = (by_abs * BLK + BLK > p.Ho) || (bx_abs * BLK + BLK > p.Wo);
+                // The residual has the output's geometry and plane count: the 1-KiB row a wave is about to store is the row it reads, at the same lane
+                // offset (a masked store's out-of-range offset masks the load too: it returns zeros).  Every element is read by the lane that writes
+                // it, before it writes it, so the output may be written over the residual.  Two pixel rows (eight loads, 32 registers) are in flight
+                // at a time -- rows 0 and 1 go out ahead of the vertical pass, row i + 2 behind row i's stores: all sixteen at once (64 registers on
+                // top of T's 96) made hipcc spill lane invariants of the CHUNK loop, with their reloads behind s_waitcnt vmcnt(0) in the matrix phase.
+                f32x4 rs[RES ? 4 : 1][RES ? 4 : 1];
+                auto load_res = [&](int i) __attribute__((always_inline)) {
+                    if constexpr (RES) {
+                        const int res_y = p.Ho - by_abs * BLK - 4 * (m_o >> 2), res_x = p.Wo - bx_abs * BLK - 4 * (m_o & 3);
+                        const __amdgpu_buffer_rsrc_t r_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.resid) + (origin - p.out_gs * w.g + p.resid_gs * w.g), 0, PLANE_BYTES, 0x00020000);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) rs[i][j] = buf_load<0>(r_res, (!partial || (i < res_y && j < res_x)) ? olane : 0x80000000u, (i * 4 + j) * 1024);
+                    }
+                };
+                load_res(0);
+                load_res(1);
                 // vertical pass: T[i][b] = sum_a A^T[i][a] M[a][b]
                 f32x4 T[4][6];
 #pragma unroll
@@ -611,6 +629,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         f32x4 o = y[j];
+                        if constexpr (RES) o = o + rs[i][j];
                         o[0] = fmaxf(o[0], floor_);
                         o[1] = fmaxf(o[1], floor_);
                         o[2] = fmaxf(o[2], floor_);
@@ -626,6 +645,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #else
                         if (o[0] == 1.2345e-30f) buf_store(o, r_out, vo, (i * 4 + j) * 1024);
 #endif
+                    }
+                    if constexpr (RES) {
+                        if (i + 2 < 4) load_res(i + 2);
                     }
                 }
             }
@@ -647,13 +669,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 hipError_t cerb_launch_wino4p(ConvParams p, hipStream_t st) {
-    if (p.Cin % CB || p.Cout % 64 || p.resid || p.pl_byp < 3 || p.pl_bxp < 3 || p.H != p.Ho || p.W != p.Wo) return hipErrorInvalidValue;
+    if (p.Cin % CB || p.Cout % 64 || (p.resid != nullptr) != (p.level_tag == 4) || p.pl_byp < 3 || p.pl_bxp < 3 || p.H != p.Ho || p.W != p.Wo) return hipErrorInvalidValue;
     const long long nblk = wino4_block_grid(p);
     if (p.pl_byp != (p.Ho + BLK - 1) / BLK + 2 || p.pl_bxp != (p.Wo + BLK - 1) / BLK + 2) return hipErrorInvalidValue;
     const long long items = (long long)p.groups * ((nblk + 1) / 2) * (p.Cout / 64);
-    const int tag = p.level_tag == 2 ? 2 : p.level_tag ? 1 : 0;
-    auto kern = tag == 2 ? conv_wino4p_kernel<2> : tag ? conv_wino4p_kernel<1> : conv_wino4p_kernel<0>;
-    static bool attr_done[3][64] = {};
+    const int tag = p.level_tag >= 2 && p.level_tag <= 4 ? p.level_tag : p.level_tag ? 1 : 0;
+    auto kern = tag == 4 ? conv_wino4p_kernel<4> : tag == 3 ? conv_wino4p_kernel<3> : tag == 2 ? conv_wino4p_kernel<2> : tag ? conv_wino4p_kernel<1> : conv_wino4p_kernel<0>;
+    static bool attr_done[5][64] = {};
     return wino4_launch(kern, attr_done[tag], items, LDS_BYTES + PROF_BYTES, p, st);
 }
 

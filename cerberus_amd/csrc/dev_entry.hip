@@ -144,4 +144,65 @@ int cerb_devfwd_upsample2_add_planar(const float* skip, const float* prev, float
     return (int)cerb_launch_upsample2_add_planar(skip, prev, out, G, N, H, W, C, prev_gs, out_gs, nullptr, prev_planar, (hipStream_t)st);
 }
 
+// ---- the encoder's tile-planar stages (bound by tests/test_encoder_planar_gpu.py): one launch at a time, NHWC against tile-planar.  The convolutions take
+// HOST weights [Cout][Cin][k][k] (BatchNorm already folded), pack them as the handle would, and free the packed copy before they return ---------------
+static int devfwd_upload(const std::vector<float>& v, float** out) {
+    if (hipMalloc((void**)out, v.size() * 4) != hipSuccess) return 1;
+    return hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess;
+}
+// 3x3 stride 1 (+ bias, + residual, ReLU): planar = 0 conv_wino4b.hip on NHWC tensors, 1 conv_wino4p.hip on tile-planar ones (`out` may be `resid`)
+int cerb_devfwd_conv3x3(const float* w_host, const float* bias, const float* in, const float* resid, float* out, int N, int H, int W, int Cin, int Cout, int relu,
+                        int planar, void* st) {
+    DEV_NEED(w_host && bias && in && out && N > 0 && H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0 && Cin % 64 == 0 && Cout % 64 == 0);
+    std::vector<float> w4;
+    cerb_host_pack_wino4(w_host, Cout, Cin, planar ? 0 : 1, &w4);
+    float* dw = nullptr;
+    DEV_NEED(devfwd_upload(w4, &dw) == 0);
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = in; p.wpack = dw; p.bias = bias; p.resid = resid; p.out = out;
+    p.N = N; p.H = p.Ho = H; p.W = p.Wo = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.groups = 1;
+    p.w_gs = (long long)Cout * Cin * 36; p.bias_gs = Cout; p.pk_off = 1;
+    p.out_gs = planar ? cerb_planar_elems(N, H, W, Cout) : (long long)N * H * W * Cout;
+    if (planar) {
+        p.level_tag = resid ? 4 : 3;
+        p.pl_byp = cerb_planar_blocks(H);
+        p.pl_bxp = cerb_planar_blocks(W);
+    }
+    hipError_t e = planar ? cerb_launch_wino4p(p, (hipStream_t)st) : cerb_launch_wino4b(p, (hipStream_t)st);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)st);
+    (void)hipFree(dw);
+    return (int)e;
+}
+// 3x3 or 1x1 stride 2 (+ bias, ReLU as asked) from an NHWC input: planar = 0 NHWC output, 1 tile-planar output (conv_igemm.hip's planar epilogue)
+int cerb_devfwd_conv_s2(const float* w_host, const float* bias, const float* in, float* out, int N, int H, int W, int Cin, int Cout, int ks, int relu, int planar, void* st) {
+    DEV_NEED(w_host && bias && in && out && N > 0 && H % 32 == 0 && W % 32 == 0 && Cin % 16 == 0 && Cout % 64 == 0 && (ks == 1 || ks == 3));
+    std::vector<float> wp;
+    cerb_host_pack_conv(w_host, Cout, Cin, ks, cerb_conv_chunk(ks, 2), &wp);
+    float* dw = nullptr;
+    DEV_NEED(devfwd_upload(wp, &dw) == 0);
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = in; p.wpack = dw; p.bias = bias; p.out = out;
+    p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.groups = 1;
+    p.w_gs = (long long)Cout * Cin * ks * ks; p.bias_gs = Cout;
+    p.out_gs = planar ? cerb_planar_elems(N, p.Ho, p.Wo, Cout) : (long long)N * p.Ho * p.Wo * Cout;
+    if (planar) {
+        p.pl_byp = cerb_planar_blocks(p.Ho);
+        p.pl_bxp = cerb_planar_blocks(p.Wo);
+    }
+    hipError_t e = cerb_launch_conv(p, ks, 2, 0, (hipStream_t)st);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)st);
+    (void)hipFree(dw);
+    return (int)e;
+}
+int cerb_devfwd_maxpool(const float* in, float* out, int N, int H, int W, int C, int planar, void* st) {
+    DEV_NEED(in && out && N > 0 && H > 0 && W > 0 && C % 4 == 0);
+    return (int)(planar ? cerb_launch_maxpool_planar(in, out, N, H, W, C, (hipStream_t)st) : cerb_launch_maxpool(in, out, N, H, W, C, (hipStream_t)st));
+}
+int cerb_devfwd_planar_to_nhwc(const float* in, float* out, int N, int H, int W, int C, void* st) {
+    DEV_NEED(in && out && N > 0);
+    return (int)cerb_launch_planar_to_nhwc(in, out, N, H, W, C, (hipStream_t)st);
+}
+
 }  // extern "C"

@@ -202,6 +202,84 @@ hipError_t cerb_launch_maxpool(const float* in, float* out, int N, int H, int W,
     return hipGetLastError();
 }
 
+// The same pooling written in the TILE-PLANAR layout (cerb_common.h) for an encoder stage that runs on conv_wino4p.hip.  The thread -> output mapping, the
+// XCD split, the window scan and the fmaxf chain are maxpool3x3s2_kernel's -- the reads (four times the bytes of the writes) stay whole 1-KiB runs per
+// wave and the values are bit-identical; only the store address differs: a wave's four pixels x 64 channels leave as sixteen 64-byte pieces, whose
+// line neighbours (the next tile to the right) are written by the next wave of the same workgroup.  A first version that gave each wave one plane of
+// a block (whole 1-KiB rows out, 64-byte pieces in) took 0.199 ms against the NHWC kernel's 0.148 ms on 32 x 256^2 x 64 (profiles/encoder_planar_ab.txt).
+// Ho and Wo are multiples of 16 (the launcher checks): no block hangs over the map, the guard ring is never touched.
+__global__ void maxpool3x3s2_planar_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int H, int W, int C, int Ho, int Wo) {
+    const long long total = (long long)N * Ho * Wo * (C / 4);
+    const int byp = cerb_planar_blocks(Ho), bxp = cerb_planar_blocks(Wo), ncc = C >> 4;
+    const long long per_xcd = gridDim.x / 8, vb = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    for (long long i = vb * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % (C / 4));
+        long long r = i / (C / 4);
+        const int ox = (int)(r % Wo);
+        r /= Wo;
+        const int oy = (int)(r % Ho);
+        const int n = (int)(r / Ho);
+        f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int y = oy * 2 - 1 + ky;
+            if (y < 0 || y >= H) continue;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int x = ox * 2 - 1 + kx;
+                if (x < 0 || x >= W) continue;
+                const f32x4 v = *reinterpret_cast<const f32x4*>(in + (((long long)n * H + y) * W + x) * C + c4 * 4);
+                m[0] = fmaxf(m[0], v[0]);
+                m[1] = fmaxf(m[1], v[1]);
+                m[2] = fmaxf(m[2], v[2]);
+                m[3] = fmaxf(m[3], v[3]);
+            }
+        }
+        *reinterpret_cast<f32x4*>(out + cerb_planar_offset(n, oy, ox, c4 >> 2, byp, bxp, ncc) + (c4 & 3) * 4) = m;
+    }
+}
+
+hipError_t cerb_launch_maxpool_planar(const float* in, float* out, int N, int H, int W, int C, hipStream_t st) {
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    if (C % 64 || (Ho & 15) || (Wo & 15) || Ho < 16 || Wo < 16) return hipErrorInvalidValue;
+    const long long total = (long long)N * Ho * Wo * (C / 4);
+    long long blocks = ((total + 255) / 256 + 7) / 8 * 8;  // a multiple of the 8 XCDs, as in cerb_launch_maxpool
+    if (blocks > 256 * 64) blocks = 256 * 64;
+    hipLaunchKernelGGL(maxpool3x3s2_planar_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, N, H, W, C, Ho, Wo);
+    return hipGetLastError();
+}
+
+// Exit of a tile-planar encoder stage: the stage's last output back to NHWC for its consumers (the next stage's stride-2 convolutions, conv_map,
+// Patch-Class, the decoder's skips).  A workgroup's turn is one 16 x 16 block x 64 channels: in each of sixteen passes its 256 threads move
+// sixteen pixels x 64 channels -- a wave writes four neighbouring pixels' 256-byte channel runs (1 KiB when C = 64) and reads the 64-byte pieces
+// of those pixels in four planes; the block's other pieces of the same lines are read by the same workgroup within the turn.
+__global__ __launch_bounds__(256) void planar_to_nhwc_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int H, int W, int C) {
+    const int ncc = C >> 4, ncb = C >> 6, nby = H >> 4, nbx = W >> 4, byp = nby + 2, bxp = nbx + 2;
+    const int q = threadIdx.x & 15, pp = threadIdx.x >> 4;  // channel quad of the 64, pixel of the pass
+    const int nwork = N * nby * nbx * ncb;
+    for (int wk = blockIdx.x; wk < nwork; wk += gridDim.x) {
+        const int blk = wk / ncb, cb = wk % ncb;
+        const int bx = blk % nbx, r_ = blk / nbx, by = r_ % nby, n = r_ / nby;
+        const float* ib = in + ((((long long)n * byp + by + 1) * bxp + bx + 1) * ncc + cb * 4 + (q >> 2)) * 4096 + (q & 3) * 4;
+        float* ob = out + (((long long)n * H + 16 * by) * W + 16 * bx) * C + cb * 64 + q * 4;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int y = k, x = pp;  // pass k = pixel row k of the block
+            const f32x4 v = *reinterpret_cast<const f32x4*>(ib + (((y & 3) * 4 + (x & 3)) * 16 + (y >> 2) * 4 + (x >> 2)) * 16);
+            *reinterpret_cast<f32x4*>(ob + ((long long)y * W + x) * C) = v;
+        }
+    }
+}
+
+hipError_t cerb_launch_planar_to_nhwc(const float* in, float* out, int N, int H, int W, int C, hipStream_t st) {
+    if (C % 64 || (H & 15) || (W & 15) || H < 16 || W < 16) return hipErrorInvalidValue;
+    const long long nwork = (long long)N * (H / 16) * (W / 16) * (C / 64);
+    if (nwork >= (1ll << 31)) return hipErrorInvalidValue;
+    const long long blocks = nwork < 256 * 16 ? nwork : 256 * 16;
+    hipLaunchKernelGGL(planar_to_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, out, N, H, W, C);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Decoder entry: out[g][n] = skip[n] + upsample2x(prev[g][n])   (reference net_layers.py:45-46 bilinear, align_corners=False;
 // net_desc.py:185-188).  HBM-bound elementwise pass feeding the Winograd conv (conv_wino.hip).  One thread = one 2x2 output
