@@ -236,6 +236,7 @@ static void pack_wino4(const float* w, int cout, int cin, std::vector<float>* ou
 
 // the host packers by themselves (dev_entry.hip: kernel-level tests launch one convolution on weights they bring)
 void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, std::vector<float>* out) { pack_conv(w, nullptr, cout, cin, ks, chunk, out); }
+void cerb_host_pack_wino(const float* w, int cout, int cin, std::vector<float>* out) { pack_wino(w, nullptr, cout, cin, out); }
 void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out) { pack_wino4(w, cout, cin, out, layout); }
 
 static int store_bn(cerb_net* net, const std::string& name, const std::vector<std::string>& bnkeys, int ch) {

@@ -350,6 +350,7 @@ struct cerb_net {
 static const int kLayers[4] = {3, 4, 6, 3};            // ResNet34 (models/backbone/resnet.py:273-286)
 static const int kFilters[5] = {64, 64, 128, 256, 512};
 void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, std::vector<float>* out);   // [cout][cin][ks][ks] -> conv_igemm.hip's stream
+void cerb_host_pack_wino(const float* w, int cout, int cin, std::vector<float>* out);                        // F(2x2,3x3) transform in conv_wino.hip's layout
 void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out);         // F(4x4,3x3) transform; layout 0 = conv_wino4 / 4p, 1 = conv_wino4b
 int prof_begin(cerb_net* net, const std::string& name, const std::string& kernel, double flops, hipStream_t st);  // per-launch records (cerb_net_profile_*)
 int prof_end(cerb_net* net, hipStream_t st);

@@ -67,7 +67,7 @@ using Item = Wino4Block;  // n: the image, or with PACKED the packed block
 template <bool HAS_RES, int STATS, bool PACKED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv_wino4b_kernel(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ __attribute__((aligned(16))) float bnred[STATS ? 4 * 16 * 8 : 4];
+    __shared__ __attribute__((aligned(16))) float bnred[STATS ? 4 * 16 * 8 * 2 : 4];  // (doubles for STATS 1: wino4_store_block)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int a = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave's 16 output channels of the item's 64 / its tile row in the input path

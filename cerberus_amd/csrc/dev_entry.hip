@@ -196,6 +196,81 @@ int cerb_devfwd_conv_s2(const float* w_host, const float* bias, const float* in,
     (void)hipFree(dw);
     return (int)e;
 }
+// ---- every forward convolution launcher on its own (tests/test_conv_forward_parity_gpu.py), the data-gradient use of cerb_train.hip included.
+// launcher: 0 cerb_launch_conv (ks 1 / 3, stride 1 / 2, mode 0 / 1), 1 cerb_launch_wino, 2 cerb_launch_wino4, 3 cerb_launch_wino4b, 4 cerb_launch_wino4p
+// (level_tag 0..4, pl_byp / pl_bxp as given; a non-zero pl_byp with launcher 0 asks for conv_igemm's planar epilogue).  w_raw: DEVICE weights
+// [G][Cout][Cin][k][k] (dgrad = 1: the forward layer's tensor, [G][Cin][Cout][3][3] in this launch's channel counts), packed here by the device packer the
+// schedule uses for that launcher (host_pack = 0; dgrad as given) or by the host packer (host_pack = 1, dgrad = 0 only); w_gs follows from the packer.
+// roi: four HOST ints (y0, y1, x0, x1) or null.  Checks what the launchers document and do not check themselves, and every channel constraint before a packer runs (the packers index whole chunks and blocks of w_raw); a launcher's error is the return code.
+// Synchronises and frees the packed copy before it returns.
+int cerb_devfwd_conv(int launcher, int ks, int stride, int mode, int level_tag, const float* w_raw, int host_pack, int dgrad, const float* in, const float* prev,
+                     const float* bias, const float* resid, float* out, double* bn_part, int G, int N, int H, int W, int Cin, int Cout, int relu, long long in_gs,
+                     long long prev_gs, long long bias_gs, long long resid_gs, long long out_gs, const int* roi, int pk_off, int pl_byp, int pl_bxp, void* st) {
+    DEV_NEED(launcher >= 0 && launcher <= 4 && w_raw && in && bias && out && G > 0 && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0);
+    DEV_NEED(!(host_pack && dgrad) && (!bn_part || launcher == 2 || launcher == 3) && ((mode == 1) == (prev != nullptr)));
+    if (launcher == 0) {  // conv_igemm.hip: whole chunks and whole 64-channel output blocks, no region of interest, no data-gradient packer
+        DEV_NEED((ks == 1 || ks == 3) && (stride == 1 || stride == 2) && (mode == 0 || (mode == 1 && ks == 3 && stride == 1 && H % 2 == 0 && W % 2 == 0)));
+        DEV_NEED(Cin % cerb_conv_chunk(ks, stride) == 0 && Cout % 64 == 0 && !roi && !dgrad && (stride == 1 || (H % 2 == 0 && W % 2 == 0)));
+    } else {  // the Winograd launchers' own channel constraints, BEFORE anything is packed: the packers index whole chunks and whole 64-channel blocks of w_raw
+        DEV_NEED(ks == 3 && stride == 1 && mode == 0 && Cin % ((launcher == 1 || launcher == 3) ? 32 : 16) == 0 && Cout % 64 == 0);
+    }
+    const hipStream_t s = (hipStream_t)st;
+    const int taps = launcher == 0 ? ks * ks : (launcher == 1 ? 16 : 36);
+    const size_t nw = (size_t)Cout * Cin * ks * ks, nu = (size_t)Cout * Cin * taps;
+    float* dw = nullptr;
+    hipError_t e = hipSuccess;
+    if (host_pack) {
+        std::vector<float> raw(nw * G), pk;
+        DEV_NEED(hipMemcpy(raw.data(), w_raw, raw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess);
+        for (int g = 0; g < G; ++g) {
+            if (launcher == 0) cerb_host_pack_conv(raw.data() + g * nw, Cout, Cin, ks, cerb_conv_chunk(ks, stride), &pk);
+            else if (launcher == 1) cerb_host_pack_wino(raw.data() + g * nw, Cout, Cin, &pk);
+            else cerb_host_pack_wino4(raw.data() + g * nw, Cout, Cin, launcher == 3 ? 1 : 0, &pk);
+        }
+        DEV_NEED(pk.size() == nu * G && devfwd_upload(pk, &dw) == 0);
+    } else {
+        DEV_NEED(hipMalloc((void**)&dw, nu * G * 4) == hipSuccess);
+        if (launcher >= 2) {
+            e = cerb_launch_pack_wino4(w_raw, dw, Cout, Cin, dgrad, launcher == 3 ? 1 : 0, G, s);
+        } else {
+            for (int g = 0; g < G && e == hipSuccess; ++g)
+                e = launcher == 0 ? cerb_launch_pack_conv(w_raw + g * nw, dw + g * nu, Cout, Cin, ks, cerb_conv_chunk(ks, stride), s)
+                                  : cerb_launch_pack_wino(w_raw + g * nw, dw + g * nu, Cout, Cin, dgrad, s);
+        }
+    }
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = in; p.prev = prev; p.wpack = dw; p.bias = bias; p.resid = resid; p.out = out; p.bn_part = bn_part;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.groups = G;
+    p.Ho = stride == 2 ? H / 2 : H;
+    p.Wo = stride == 2 ? W / 2 : W;
+    p.in_gs = in_gs; p.prev_gs = prev_gs; p.w_gs = (long long)nu; p.bias_gs = bias_gs; p.resid_gs = resid_gs; p.out_gs = out_gs;
+    if (roi) { p.roi_y0 = roi[0]; p.roi_y1 = roi[1]; p.roi_x0 = roi[2]; p.roi_x1 = roi[3]; }
+    p.pk_off = pk_off; p.level_tag = level_tag; p.pl_byp = pl_byp; p.pl_bxp = pl_bxp;
+    if (e == hipSuccess) {
+        switch (launcher) {
+            case 0: e = cerb_launch_conv(p, ks, stride, mode, s); break;
+            case 1: e = cerb_launch_wino(p, s); break;
+            case 2: e = cerb_launch_wino4(p, s); break;
+            case 3: e = cerb_launch_wino4b(p, s); break;
+            default: e = cerb_launch_wino4p(p, s); break;
+        }
+    }
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(dw);
+    return (int)e;
+}
+static ConvParams devfwd_geom(int N, int H, int W, int Cin, int Cout, int pk_off) {
+    ConvParams q;
+    memset(&q, 0, sizeof(q));
+    q.N = N; q.H = q.Ho = H; q.W = q.Wo = W; q.Cin = Cin; q.Cout = Cout; q.pk_off = pk_off;
+    return q;
+}
+// conv_wino4b's item form for a whole-map launch of this geometry, and the BatchNorm partial rows per group it leaves
+int cerb_devfwd_wino4b_packed(int N, int H, int W, int Cin, int Cout, int pk_off) { return cerb_wino4b_packed(devfwd_geom(N, H, W, Cin, Cout, pk_off)) ? 1 : 0; }
+int cerb_devfwd_wino4b_bn_blocks(int N, int H, int W, int Cin, int Cout, int pk_off) { return cerb_wino4b_bn_blocks(devfwd_geom(N, H, W, Cin, Cout, pk_off)); }
+
 int cerb_devfwd_maxpool(const float* in, float* out, int N, int H, int W, int C, int planar, void* st) {
     DEV_NEED(in && out && N > 0 && H > 0 && W > 0 && C % 4 == 0);
     return (int)(planar ? cerb_launch_maxpool_planar(in, out, N, H, W, C, (hipStream_t)st) : cerb_launch_maxpool(in, out, N, H, W, C, (hipStream_t)st));

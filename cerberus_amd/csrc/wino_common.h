@@ -94,7 +94,7 @@ struct Wino4Block {
 // directly, one instruction touches 16 partial cache lines and takes ~300 cycles to issue with the matrix pipe idle.  The waves therefore transpose
 // the block through `stg` (a V buffer the last chunk has finished with) into [pixel][64 channels] and store whole pixel rows -- 1 KiB contiguous
 // (4 pixels x 256 bytes) per instruction -- with residual, ReLU floor and, for training, the BatchNorm partials of ConvParams::bn_part through `bnred`
-// (4 * 16 * 8 floats of LDS): STATS 1 = (sum, sum of squares) of the outputs, STATS 2 = the BatchNorm-backward sums (ConvParams::bst_*).
+// (4 * 16 * 8 doubles of LDS, 16-byte aligned): STATS 1 = (sum, sum of squares) of the outputs, summed in double; STATS 2 = the BatchNorm-backward sums (ConvParams::bst_*).
 // PACKED (conv_wino4b.hip): the block's 16 tiles are tiles 16 n .. 16 n + 15 of the group, placed by pk_decode(tile, n, ty, tx); rows leave per tile.
 // dead: nothing is stored or counted (the repeated second block of conv_wino4.hip's last pair); every wave still meets both barriers.
 // lane_o: the lane id, made opaque per item by the caller (keeps what derives from it out of the matrix phase's register budget).
@@ -175,7 +175,12 @@ __device__ __forceinline__ void wino4_store_block(const ConvParams& p, float* st
         bga = *reinterpret_cast<const f32x4*>(p.bst_gamma + pc);
         bbe = *reinterpret_cast<const f32x4*>(p.bst_beta + pc);
     }
-    f32x4 bts = {0.f, 0.f, 0.f, 0.f}, btq = {0.f, 0.f, 0.f, 0.f};  // STATS: this lane's 16 pixels x 4 channels
+    f32x4 bts = {0.f, 0.f, 0.f, 0.f}, btq = {0.f, 0.f, 0.f, 0.f};  // STATS 2: this lane's 16 pixels x 4 channels
+    // STATS 1: (sum, sum of squares) in double from the first addition on -- the partial rows are doubles, and a float sum over a block's 256 pixels put the
+    // variance 2e-7 .. 4e-7 (relative) from the float64 statistics of the very output stored here, up to 5.5 x torch's float32 error
+    // (tests/test_conv_forward_parity_gpu.py); `bnred` then holds [wave][channel quad][4 sums, 4 sums of squares] DOUBLES
+    double dts[4] = {0.0, 0.0, 0.0, 0.0}, dtq[4] = {0.0, 0.0, 0.0, 0.0};
+    double* bnred_d = reinterpret_cast<double*>(bnred);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         f32x4 o = *reinterpret_cast<const f32x4*>(stg + sr + (16 * (k >> 2) + 4 * (k & 3)) * OPX);
@@ -187,11 +192,12 @@ __device__ __forceinline__ void wino4_store_block(const ConvParams& p, float* st
         const bool rowok = !partial || (by0 + 4 * a + (k >> 2) < p.Ho);
         if constexpr (STATS == 1) {
             if (rowok && vo[k & 3] != 0x80000000u) {  // pixels inside the image only
-                bts = bts + o;
-                btq[0] = fmaf(o[0], o[0], btq[0]);
-                btq[1] = fmaf(o[1], o[1], btq[1]);
-                btq[2] = fmaf(o[2], o[2], btq[2]);
-                btq[3] = fmaf(o[3], o[3], btq[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double od = (double)o[e];
+                    dts[e] += od;
+                    dtq[e] = fma(od, od, dtq[e]);
+                }
             }
         }
         if constexpr (STATS == 2) {
@@ -211,7 +217,23 @@ __device__ __forceinline__ void wino4_store_block(const ConvParams& p, float* st
 #endif
         buf_store<ST_AUX>(o, r_out, rowok ? vo[k & 3] : 0x80000000u, (k >> 2) * orow + (PACKED ? 0 : 4 * (k & 3) * opix));
     }
-    if constexpr (STATS) {  // the four lanes that hold a channel quad, then (behind the barrier) the four waves = the block's 256 pixels
+    if constexpr (STATS == 1) {  // the four lanes that hold a channel quad, then (behind the barrier) the four waves = the block's 256 pixels
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            dts[e] += __shfl_xor(dts[e], 16);
+            dts[e] += __shfl_xor(dts[e], 32);
+            dtq[e] += __shfl_xor(dtq[e], 16);
+            dtq[e] += __shfl_xor(dtq[e], 32);
+        }
+        if (lane_o < 16) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                bnred_d[(a * 16 + lane_o) * 8 + e] = dts[e];
+                bnred_d[(a * 16 + lane_o) * 8 + 4 + e] = dtq[e];
+            }
+        }
+    }
+    if constexpr (STATS == 2) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             bts[e] += __shfl_xor(bts[e], 16);
@@ -231,10 +253,19 @@ __device__ __forceinline__ void wino4_store_block(const ConvParams& p, float* st
         if (a == 0 && lane_o < 16 && !dead && p.bn_part) {
             const long long blk = PACKED ? (long long)w.n : ((long long)w.n * p.tiles_y + w.by) * p.tiles_x + w.bx;
             double* dst = p.bn_part + (((long long)w.g * p.bn_bpg + blk) * p.Cout + w.cb * 64 + 4 * lane_o) * 2;
+            if constexpr (STATS == 1) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                dst[2 * e] = (double)(((bnred[lane_o * 8 + e] + bnred[(16 + lane_o) * 8 + e]) + bnred[(32 + lane_o) * 8 + e]) + bnred[(48 + lane_o) * 8 + e]);
-                dst[2 * e + 1] = (double)(((bnred[lane_o * 8 + 4 + e] + bnred[(16 + lane_o) * 8 + 4 + e]) + bnred[(32 + lane_o) * 8 + 4 + e]) + bnred[(48 + lane_o) * 8 + 4 + e]);
+                for (int e = 0; e < 4; ++e) {
+                    dst[2 * e] = ((bnred_d[lane_o * 8 + e] + bnred_d[(16 + lane_o) * 8 + e]) + bnred_d[(32 + lane_o) * 8 + e]) + bnred_d[(48 + lane_o) * 8 + e];
+                    dst[2 * e + 1] = ((bnred_d[lane_o * 8 + 4 + e] + bnred_d[(16 + lane_o) * 8 + 4 + e]) + bnred_d[(32 + lane_o) * 8 + 4 + e]) + bnred_d[(48 + lane_o) * 8 + 4 + e];
+                }
+            }
+            if constexpr (STATS == 2) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    dst[2 * e] = (double)(((bnred[lane_o * 8 + e] + bnred[(16 + lane_o) * 8 + e]) + bnred[(32 + lane_o) * 8 + e]) + bnred[(48 + lane_o) * 8 + e]);
+                    dst[2 * e + 1] = (double)(((bnred[lane_o * 8 + 4 + e] + bnred[(16 + lane_o) * 8 + 4 + e]) + bnred[(32 + lane_o) * 8 + 4 + e]) + bnred[(48 + lane_o) * 8 + 4 + e]);
+                }
             }
         }
     }

@@ -1,5 +1,6 @@
 """ctypes bindings of the test-only entry layer of libcerberus_hip_dev.so (cerberus_amd/csrc/dev_entry.hip: cerb_dev_<kernel> wrappers over single
-launchers of cerb_net.h) and the helpers that lay tensors out as the kernels expect.  Developer code: it lives under tests/, and works only in the
+launchers of cerb_net.h for the training backward, cerb_devfwd_<kernel> for the forward path: cerb_devfwd_conv drives any one forward convolution launcher)
+and the helpers that lay tensors out as the kernels expect, the tile-planar layout included.  Developer code: it lives under tests/, and works only in the
 child process of a `dev_switches` test (CERB_DEV_LIB=1), where cerberus_amd loads the developers' library.
 
 Layouts: activations NHWC with a leading group axis [G][N][H][W][C]; weights [G][Cout][Cin][k][k].
@@ -47,6 +48,17 @@ _SIGS = {
     "cerb_dev_crop_gap": (_I, [_P] + [_I] * 8 + [_P, _P]),
     "cerb_dev_crop_gap_bwd": (_I, [_P, _P] + [_I] * 8 + [_P]),
     "cerb_dev_dilate2": (_I, [_P, _P, _LL, _I, _I, _I, _P]),
+    # the forward path, one launcher at a time (cerb_devfwd_*)
+    "cerb_devfwd_planar_elems": (_LL, [_I] * 4),
+    "cerb_devfwd_upsample2_add": (_I, [_P] * 3 + [_I] * 5 + [_LL, _P]),
+    "cerb_devfwd_upsample2_add_planar": (_I, [_P] * 3 + [_I] * 5 + [_LL, _LL, _I, _P]),
+    "cerb_devfwd_conv3x3": (_I, [_P] * 5 + [_I] * 7 + [_P]),
+    "cerb_devfwd_conv_s2": (_I, [_P] * 4 + [_I] * 8 + [_P]),
+    "cerb_devfwd_maxpool": (_I, [_P] * 2 + [_I] * 5 + [_P]),
+    "cerb_devfwd_planar_to_nhwc": (_I, [_P] * 2 + [_I] * 4 + [_P]),
+    "cerb_devfwd_conv": (_I, [_I] * 5 + [_P, _I, _I] + [_P] * 6 + [_I] * 7 + [_LL] * 5 + [C.POINTER(C.c_int)] + [_I] * 3 + [_P]),
+    "cerb_devfwd_wino4b_packed": (_I, [_I] * 6),
+    "cerb_devfwd_wino4b_bn_blocks": (_I, [_I] * 6),
 }
 ENTRIES = sorted(_SIGS)
 _lib = None
@@ -132,3 +144,35 @@ def banded(t, W):
 def ok(rc, what):
     assert rc == 0, "%s returned hipError %d" % (what, rc)
     torch.cuda.synchronize()
+
+
+# ---- the tile-planar layout (cerb_common.h: cerb_planar_offset) --------------------------------------------------------------------------------------
+def _planar_idx(n, h, w, c):
+    """float index of every element of an [n][h][w][c] tensor in its tile-planar buffer (cerb_common.h: cerb_planar_offset), and the buffer's size"""
+    byp, bxp, ncc = (h + 15) // 16 + 2, (w + 15) // 16 + 2, c // 16
+    y, x = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+    off = (((y // 16 + 1) * bxp + x // 16 + 1) * ncc) * 4096 + (((y % 4) * 4 + x % 4) * 16 + ((y // 4) % 4) * 4 + (x // 4) % 4) * 16
+    per_image = byp * bxp * ncc * 4096
+    ch = torch.arange(c)
+    idx = torch.arange(n).view(n, 1, 1, 1) * per_image + off.view(1, h, w, 1) + (ch // 16 * 4096 + ch % 16).view(1, 1, 1, c)
+    return idx.cuda(), n * per_image
+
+
+def _to_planar(t):
+    n, h, w, c = t.shape
+    idx, size = _planar_idx(n, h, w, c)
+    buf = torch.zeros(size, device="cuda")
+    buf[idx] = t
+    return buf
+
+
+def _check_planar(buf, ref, what):
+    """every pixel of the tile-planar buffer equals the NHWC reference, whatever no pixel maps to (the guard ring) is zero"""
+    n, h, w, c = ref.shape
+    idx, size = _planar_idx(n, h, w, c)
+    assert buf.numel() == size, what
+    got = buf[idx]
+    assert torch.equal(got, ref), (what, int((got != ref).sum()))
+    written = torch.zeros(size, dtype=torch.bool, device="cuda")
+    written[idx.reshape(-1)] = True
+    assert bool((buf[~written] == 0).all()), (what, "guard ring")

@@ -4,7 +4,9 @@ Every operation is torch.nn.functional under autograd on the SAME inputs the ker
 float32 the yardstick `ref32` of the kernel's bar (err(kernel) <= k * err(ref32) + 1e-7 with err(a) = max|a - ref64| / max|ref64| per tensor).
 Activations are NHWC with a leading group axis [G][N][H][W][C], weights [G][Cout][Cin][k][k] -- the kernels' own layouts (tests/dev_kernels.py).
 Two references are written by hand: wgrad_wino_formula (the F(4x4,3x3) Winograd-domain weight gradient, the second yardstick of that kernel) and
-dilate2; tests/test_kernel_refs.py ties both to autograd on the host."""
+dilate2; tests/test_kernel_refs.py ties both to autograd on the host.  The forward convolutions (tests/test_conv_forward_parity_gpu.py) have conv_forward
+(F.conv2d + bias + residual + ReLU, the decoder entry in front of it) and wino_forward_formula, the F(2x2) / F(4x4) algorithm of the Winograd kernels
+evaluated plainly: the yardstick of those kernels, tied to conv2d in the same host test."""
 import torch
 import torch.nn.functional as F
 
@@ -65,6 +67,68 @@ def wgrad_wino_formula(x, dy, dt):
         Z = torch.einsum("ji,ncjkt,kl->ncilt", AT, q, AT)
         dU = torch.einsum("noabt,niabt->oiab", Z, V)
         out.append(torch.einsum("ax,oiab,by->oixy", Gm, dU, Gm))
+    return torch.stack(out)
+
+
+# ---- forward convolutions -------------------------------------------------------------------------------------------------------------------------
+def upadd(skip, prev, dt):
+    """skip [N][H][W][C] + bilinear x2 (align_corners=False) of prev [N][H/2][W/2][C], NHWC in and out (the decoder entry, as in upadd_grads)"""
+    up = F.interpolate(prev.permute(0, 3, 1, 2).to(dt), scale_factor=2, mode="bilinear", align_corners=False)
+    return skip.to(dt) + up.permute(0, 2, 3, 1)
+
+
+def conv_epilogue(y, bias, resid, relu, dt):
+    """y [G][N][Ho][Wo][Cout] (+ bias [G or 1][Cout]) (+ resid, same shape) -> ReLU as asked, in dt"""
+    y = y.to(dt)
+    if bias is not None:
+        y = y + bias.to(dt).view(bias.shape[0], 1, 1, 1, -1)
+    if resid is not None:
+        y = y + resid.to(dt)
+    return torch.relu(y) if relu else y
+
+
+def conv_forward(x, w, bias, resid, prev, ks, stride, relu, dt):
+    """x [G or 1][N][H][W][Cin] (1: every group reads the same input), w [G][Cout][Cin][ks][ks], bias [G or 1][Cout] or None, resid [G][N][Ho][Wo][Cout] or
+    None, prev [G or 1][N][H/2][W/2][Cin] or None (then the input of group g is x + bilinear x2 of prev) -> [G][N][Ho][Wo][Cout]: F.conv2d with padding
+    ks // 2, + bias, + residual, ReLU as asked.  float64 is the reference, float32 the yardstick of the direct kernel."""
+    out = []
+    for g in range(w.shape[0]):
+        xg = x[min(g, x.shape[0] - 1)]
+        xg = xg.to(dt) if prev is None else upadd(xg, prev[min(g, prev.shape[0] - 1)], dt)
+        out.append(F.conv2d(xg.permute(0, 3, 1, 2).contiguous(), w[g].to(dt), None, stride=stride, padding=ks // 2).permute(0, 2, 3, 1))
+    return conv_epilogue(torch.stack(out), bias, resid, relu, dt)
+
+
+def dgrad_filter(w):
+    """w [G][Cout][Cin][3][3] -> the data-gradient filter [G][Cin][Cout][3][3], W'[ci][co][tap] = W[co][ci][8 - tap] (rotated by 180 degrees, transposed)"""
+    return w.flip(-1, -2).transpose(1, 2).contiguous()
+
+
+_BT2 = [[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]]
+_G2 = [[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]]
+_AT2 = [[1, 1, 1, 0], [0, 1, -1, -1]]
+
+
+def wino_forward_formula(x, w, m, dt):
+    """The algorithm of the Winograd convolution kernels evaluated plainly in `dt`: Y = A^T [(G g G^T) .* (B^T d B), summed over the input channels] A per
+    m x m output tile, m = 2 (conv_wino.hip; the matrices of its packer) or m = 4 (conv_wino4*.hip; the matrices above).  The filter transform runs in
+    double and is rounded once to dt, as the packers do; maps that are no multiple of m are zero-extended.  x [G or 1][N][H][W][Cin],
+    w [G][Cout][Cin][3][3] -> [G][N][H][W][Cout] (3x3, stride 1, zero padding 1; no bias)."""
+    bt, gm, at = (_BT2, _G2, _AT2) if m == 2 else (_BT, _G, _AT)
+    BT, AT, Gm = torch.tensor(bt, dtype=dt), torch.tensor(at, dtype=dt), torch.tensor(gm, dtype=torch.float64)
+    out = []
+    for g in range(w.shape[0]):
+        xg = x[min(g, x.shape[0] - 1)].permute(0, 3, 1, 2).to(dt)
+        N, Ci, H, W = xg.shape
+        Hp, Wp = (H + m - 1) // m * m, (W + m - 1) // m * m
+        T = (Hp // m) * (Wp // m)
+        U = torch.einsum("ax,oixy,by->oiab", Gm, w[g].to(torch.float64), Gm).to(dt)
+        d = F.unfold(F.pad(xg, (1, 1 + Wp - W, 1, 1 + Hp - H)), m + 2, stride=m).view(N, Ci, m + 2, m + 2, T)
+        V = torch.einsum("ij,ncjkt,lk->ncilt", BT, d, BT)
+        M = torch.einsum("oiab,niabt->noabt", U, V)
+        Y = torch.einsum("ia,noabt,jb->noijt", AT, M, AT)
+        y = F.fold(Y.reshape(N, -1, T), (Hp, Wp), m, stride=m)
+        out.append(y[:, :, :H, :W].permute(0, 2, 3, 1))
     return torch.stack(out)
 
 

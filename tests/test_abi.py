@@ -95,12 +95,12 @@ def test_product_library_exports_no_developer_entry():
     assert os.path.exists(_lib.LIB_PATH) and os.path.exists(build.LIB_DEV), "run `python -m cerberus_amd.build` first"
     prod = _exported(build.LIB)
     assert "cerb_net_forward" in prod and "cerb_adam_step" in prod  # (the parser sees the exports)
-    assert [n for n in prod if n.startswith("cerb_dev_")] == []
+    assert [n for n in prod if n.startswith(("cerb_dev_", "cerb_devfwd_"))] == []
     dev = _exported(build.LIB_DEV)
     src = open(os.path.join(ROOT, "cerberus_amd", "csrc", "dev_entry.hip")).read()
-    declared = sorted(set(re.findall(r"\b(cerb_dev_[a-z0-9_]+)\s*\(", re.sub(r"//[^\n]*", "", src))))
-    assert declared == dev_kernels.ENTRIES and len(declared) >= 25
-    assert sorted(n for n in dev if n.startswith("cerb_dev_")) == declared
+    declared = sorted(set(re.findall(r"\b(cerb_dev(?:fwd)?_[a-z0-9_]+)\s*\(", re.sub(r"//[^\n]*", "", src))))
+    assert declared == dev_kernels.ENTRIES and len(declared) >= 35
+    assert sorted(n for n in dev if n.startswith(("cerb_dev_", "cerb_devfwd_"))) == declared
     assert "dev_entry.hip" in build.DEV_ONLY_SOURCES and "dev_entry.hip" not in build.SOURCES
 
 

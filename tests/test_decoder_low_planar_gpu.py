@@ -6,7 +6,6 @@ the bits of the NHWC path: torch.equal on every output of every head and on the 
 Shapes: the smallest at which the new paths can go wrong -- one block per image at the lowest level (tile 128), an odd number of blocks there (the last
 pair of a conv_wino4p item repeats a block), maps whose sides are multiples of 4 but not of 16 (tile 160: blocks hang over the map, the guard ring and the
 never-written pixels must stay zero, also after a larger batch has used the same buffers), and a grouped launch of two decoders instead of five."""
-import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -116,11 +115,7 @@ def test_entry_pass_matches_the_nhwc_kernel_bit_for_bit(c):
     per group; whatever no pixel maps to (guard ring, pixels beyond the map) is still zero."""
     import dev_kernels as D
 
-    L = D.lib()
-    _P, _I, _LL = C.c_void_p, C.c_int, C.c_longlong
-    L.cerb_devfwd_planar_elems.restype, L.cerb_devfwd_planar_elems.argtypes = _LL, [_I] * 4
-    L.cerb_devfwd_upsample2_add.restype, L.cerb_devfwd_upsample2_add.argtypes = _I, [_P] * 3 + [_I] * 5 + [_LL, _P]
-    L.cerb_devfwd_upsample2_add_planar.restype, L.cerb_devfwd_upsample2_add_planar.argtypes = _I, [_P] * 3 + [_I] * 5 + [_LL, _LL, _I, _P]
+    L = D.lib()   # (dev_kernels._SIGS declares the signatures of the cerb_devfwd_* entries)
     G, N, H, W = 2, 2, 20, 20
     g = torch.Generator().manual_seed(c)
     skip = torch.randn((N, H, W, c), generator=g).cuda()

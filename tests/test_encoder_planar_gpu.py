@@ -15,7 +15,9 @@ import numpy as np
 import pytest
 import torch
 
+import dev_kernels as D
 from conftest import dev_switches
+from dev_kernels import _check_planar, _to_planar
 
 pytestmark = pytest.mark.gpu
 
@@ -130,50 +132,9 @@ def test_a_map_that_is_no_multiple_of_16_stays_nhwc():
 
 
 # ---- kernel level, through the developers' library ---------------------------------------------------------------------------------------------------
-_P, _I, _LL = C.c_void_p, C.c_int, C.c_longlong
-
-
 def _dev():
-    import dev_kernels as D
-
-    L = D.lib()
-    L.cerb_devfwd_planar_elems.restype, L.cerb_devfwd_planar_elems.argtypes = _LL, [_I] * 4
-    L.cerb_devfwd_conv3x3.restype, L.cerb_devfwd_conv3x3.argtypes = _I, [_P] * 5 + [_I] * 7 + [_P]
-    L.cerb_devfwd_conv_s2.restype, L.cerb_devfwd_conv_s2.argtypes = _I, [_P] * 4 + [_I] * 8 + [_P]
-    L.cerb_devfwd_maxpool.restype, L.cerb_devfwd_maxpool.argtypes = _I, [_P] * 2 + [_I] * 5 + [_P]
-    L.cerb_devfwd_planar_to_nhwc.restype, L.cerb_devfwd_planar_to_nhwc.argtypes = _I, [_P] * 2 + [_I] * 4 + [_P]
-    return D, L
-
-
-def _planar_idx(n, h, w, c):
-    """float index of every element of an [n][h][w][c] tensor in its tile-planar buffer (cerb_common.h: cerb_planar_offset), and the buffer's size"""
-    byp, bxp, ncc = h // 16 + 2, w // 16 + 2, c // 16
-    y, x = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-    off = (((y // 16 + 1) * bxp + x // 16 + 1) * ncc) * 4096 + (((y % 4) * 4 + x % 4) * 16 + ((y // 4) % 4) * 4 + (x // 4) % 4) * 16
-    per_image = byp * bxp * ncc * 4096
-    ch = torch.arange(c)
-    idx = torch.arange(n).view(n, 1, 1, 1) * per_image + off.view(1, h, w, 1) + (ch // 16 * 4096 + ch % 16).view(1, 1, 1, c)
-    return idx.cuda(), n * per_image
-
-
-def _to_planar(t):
-    n, h, w, c = t.shape
-    idx, size = _planar_idx(n, h, w, c)
-    buf = torch.zeros(size, device="cuda")
-    buf[idx] = t
-    return buf
-
-
-def _check_planar(buf, ref, what):
-    """every pixel of the tile-planar buffer equals the NHWC reference, whatever no pixel maps to (the guard ring) is zero"""
-    n, h, w, c = ref.shape
-    idx, size = _planar_idx(n, h, w, c)
-    assert buf.numel() == size, what
-    got = buf[idx]
-    assert torch.equal(got, ref), (what, int((got != ref).sum()))
-    written = torch.zeros(size, dtype=torch.bool, device="cuda")
-    written[idx.reshape(-1)] = True
-    assert bool((buf[~written] == 0).all()), (what, "guard ring")
+    """the bindings module and the developers' library; dev_kernels._SIGS declares the signatures of the cerb_devfwd_* entries used here"""
+    return D, D.lib()
 
 
 @dev_switches
