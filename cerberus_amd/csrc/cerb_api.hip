@@ -239,6 +239,75 @@ void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, s
 void cerb_host_pack_wino(const float* w, int cout, int cin, std::vector<float>* out) { pack_wino(w, nullptr, cout, cin, out); }
 void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out) { pack_wino4(w, cout, cin, out, layout); }
 
+// The stem's stream [7 ky][12 t][2 s][64 lane] (stem_conv7x7_kernel): lane (l & 31, l >> 5) of step t holds output channel 32 s + (l & 31) at
+// k = 2 t + (l >> 5) = 3 kx + c, zero for k >= 21.  w [64][3][7][7], scale [64] (the folded BatchNorm; ones in a training handle).
+void cerb_host_pack_stem(const float* w, const float* scale, std::vector<float>* out) {
+    std::vector<float>& wp = *out;
+    wp.assign(7 * 12 * 2 * 64, 0.f);
+    for (int ky = 0; ky < 7; ++ky)
+        for (int t = 0; t < 12; ++t)
+            for (int s = 0; s < 2; ++s)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int co = s * 32 + (lane & 31), kk = 2 * t + (lane >> 5);
+                    float v = 0.f;
+                    if (kk < 21) {
+                        const int kx = kk / 3, c = kk % 3;
+                        v = w[(((size_t)co * 3 + c) * 7 + ky) * 7 + kx] * scale[co];
+                    }
+                    wp[((ky * 12 + t) * 2 + s) * 64 + lane] = v;
+                }
+}
+
+// One output head: w1 [96][64], b1 [96], scale / shift [96] (the folded BatchNorm behind the first 1x1), w2 [out_ch][96], b2 [out_ch].
+// layouts of head_kernel (v_mfma_f32_16x16x4_f32, lane = (row/col l & 15, k-slot l >> 4)):
+//   w1p[blk 6][g 4][lane][t]  = W1[16 blk + (l & 15)][16 g + 4 (l >> 4) + t]  (BN folded)
+//   w2p[blk 6][lane][r]       = W2[l & 15][16 blk + 4 (l >> 4) + r]           (rows >= out_ch are zero)
+//   w2q[set 2][blk 6][lane][r] = W2[4 set + (l & 3)][16 blk + 4 (l >> 4) + r]   (head_group_kernel<true>: v_mfma_f32_4x4x1_16B_f32)
+void cerb_host_pack_head(const float* w1, const float* b1, const float* scale, const float* shift, const float* w2, const float* b2, int out_ch,
+                         std::vector<float>* w1p_out, std::vector<float>* b1p_out, std::vector<float>* w2p_out, std::vector<float>* b2p_out,
+                         std::vector<float>* w2q_out) {
+    std::vector<float>&w1p = *w1p_out, &b1p = *b1p_out, &w2p = *w2p_out, &b2p = *b2p_out, &w2q = *w2q_out;
+    w1p.assign(6 * 4 * 64 * 4, 0.f); b1p.assign(96, 0.f); w2p.assign(6 * 64 * 4, 0.f); b2p.assign(32, 0.f);
+    for (int blk = 0; blk < 6; ++blk)
+        for (int G = 0; G < 4; ++G)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int t = 0; t < 4; ++t) {
+                    const int hid = blk * 16 + (lane & 15), ci = G * 16 + 4 * (lane >> 4) + t;
+                    w1p[((blk * 4 + G) * 64 + lane) * 4 + t] = w1[(size_t)hid * 64 + ci] * scale[hid];
+                }
+    for (int c = 0; c < 96; ++c) b1p[c] = b1[c] * scale[c] + shift[c];
+    for (int blk = 0; blk < 6; ++blk)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int r = 0; r < 4; ++r) {
+                const int o = lane & 15, hid = blk * 16 + 4 * (lane >> 4) + r;
+                w2p[(blk * 64 + lane) * 4 + r] = (o < out_ch) ? w2[(size_t)o * 96 + hid] : 0.f;
+            }
+    for (int c = 0; c < out_ch; ++c) b2p[c] = b2[c];
+    w2q.assign(2 * 24 * 64, 0.f);
+    for (int set = 0; set < 2; ++set)
+        for (int blk = 0; blk < 6; ++blk)
+            for (int r = 0; r < 4; ++r)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int o = 4 * set + (lane & 3), hid = blk * 16 + 4 * (lane >> 4) + r;
+                    if (o < out_ch) w2q[((set * 6 + blk) * 64 + lane) * 4 + r] = w2[(size_t)o * 96 + hid];
+                }
+}
+
+// Patch-Class: w1 [256][512] with bn2's scale / shift [256] folded in, transposed to [512][256]; w2 [out_ch][256] transposed and padded to [256][16]
+void cerb_host_pack_patch_class(const float* w1, const float* b1, const float* scale2, const float* shift2, const float* w2, const float* b2, int out_ch,
+                                std::vector<float>* w1t_out, std::vector<float>* b1f_out, std::vector<float>* w2t_out, std::vector<float>* b2f_out) {
+    std::vector<float>&w1t = *w1t_out, &b1f = *b1f_out, &w2t = *w2t_out, &b2f = *b2f_out;
+    w1t.assign(512 * 256, 0.f); b1f.assign(256, 0.f); w2t.assign(256 * 16, 0.f); b2f.assign(16, 0.f);
+    for (int o = 0; o < 256; ++o) {
+        for (int c = 0; c < 512; ++c) w1t[(size_t)c * 256 + o] = w1[(size_t)o * 512 + c] * scale2[o];
+        b1f[o] = b1[o] * scale2[o] + shift2[o];
+    }
+    for (int o = 0; o < out_ch; ++o) {
+        for (int c = 0; c < 256; ++c) w2t[(size_t)c * 16 + o] = w2[(size_t)o * 256 + c];
+        b2f[o] = b2[o];
+    }
+}
+
 static int store_bn(cerb_net* net, const std::string& name, const std::vector<std::string>& bnkeys, int ch) {
     std::vector<float> ga, be;
     for (const std::string& k : bnkeys) {
@@ -364,19 +433,8 @@ extern "C" int cerb_net_finalize(cerb_net* net) {
             f.shift.assign(64, 0.f);
             if (store_bn(net, "stem", {"backbone.bn1"}, 64)) return 1;
         }
-        std::vector<float> wp(7 * 12 * 2 * 64, 0.f);
-        for (int ky = 0; ky < 7; ++ky)
-            for (int t = 0; t < 12; ++t)
-                for (int s = 0; s < 2; ++s)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int co = s * 32 + (lane & 31), kk = 2 * t + (lane >> 5);
-                        float v = 0.f;
-                        if (kk < 21) {
-                            const int kx = kk / 3, c = kk % 3;
-                            v = w->data[(((size_t)co * 3 + c) * 7 + ky) * 7 + kx] * f.scale[co];
-                        }
-                        wp[((ky * 12 + t) * 2 + s) * 64 + lane] = v;
-                    }
+        std::vector<float> wp;
+        cerb_host_pack_stem(w->data.data(), f.scale.data(), &wp);
         if (upload(net, wp, &net->stem_w) || upload(net, f.shift, &net->stem_b)) return 1;
         if (!net->fold_bn) {
             if (upload(net, w->data, &net->stem_raw)) return 1;
@@ -425,34 +483,8 @@ extern "C" int cerb_net_finalize(cerb_net* net) {
                 bn_fold(net, p + ".0.block.0.bn", 96, &f) || get(net, p + ".1.conv.weight", {d.out_ch, 96, 1, 1}, &w2) ||
                 get(net, p + ".1.conv.bias", {d.out_ch}, &b2))
                 return 1;
-            // layouts of head_kernel (v_mfma_f32_16x16x4_f32, lane = (row/col l & 15, k-slot l >> 4)):
-            //   w1p[blk 6][g 4][lane][t]  = W1[16 blk + (l & 15)][16 g + 4 (l >> 4) + t]  (BN folded)
-            //   w2p[blk 6][lane][r]       = W2[l & 15][16 blk + 4 (l >> 4) + r]           (rows >= out_ch are zero)
-            std::vector<float> w1p(6 * 4 * 64 * 4), b1p(96), w2p(6 * 64 * 4, 0.f), b2p(32, 0.f);
-            for (int blk = 0; blk < 6; ++blk)
-                for (int G = 0; G < 4; ++G)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int t = 0; t < 4; ++t) {
-                            const int hid = blk * 16 + (lane & 15), ci = G * 16 + 4 * (lane >> 4) + t;
-                            w1p[((blk * 4 + G) * 64 + lane) * 4 + t] = w1->data[(size_t)hid * 64 + ci] * f.scale[hid];
-                        }
-            for (int c = 0; c < 96; ++c) b1p[c] = b1->data[c] * f.scale[c] + f.shift[c];
-            for (int blk = 0; blk < 6; ++blk)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int o = lane & 15, hid = blk * 16 + 4 * (lane >> 4) + r;
-                        w2p[(blk * 64 + lane) * 4 + r] = (o < d.out_ch) ? w2->data[(size_t)o * 96 + hid] : 0.f;
-                    }
-            for (int c = 0; c < d.out_ch; ++c) b2p[c] = b2->data[c];
-            //   w2q[set 2][blk 6][lane][r] = W2[4 set + (l & 3)][16 blk + 4 (l >> 4) + r]   (head_group_kernel<true>: v_mfma_f32_4x4x1_16B_f32)
-            std::vector<float> w2q(2 * 24 * 64, 0.f);
-            for (int set = 0; set < 2; ++set)
-                for (int blk = 0; blk < 6; ++blk)
-                    for (int r = 0; r < 4; ++r)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int o = 4 * set + (lane & 3), hid = blk * 16 + 4 * (lane >> 4) + r;
-                            if (o < d.out_ch) w2q[((set * 6 + blk) * 64 + lane) * 4 + r] = w2->data[(size_t)o * 96 + hid];
-                        }
+            std::vector<float> w1p, b1p, w2p, b2p, w2q;
+            cerb_host_pack_head(w1->data.data(), b1->data.data(), f.scale.data(), f.shift.data(), w2->data.data(), b2->data.data(), d.out_ch, &w1p, &b1p, &w2p, &b2p, &w2q);
             if (!net->fold_bn) {
                 float *r1, *rb1, *r2, *rb2;
                 if (upload(net, w1->data, &r1) || upload(net, b1->data, &rb1) || upload(net, w2->data, &r2) || upload(net, b2->data, &rb2)) return 1;
@@ -487,15 +519,8 @@ extern "C" int cerb_net_finalize(cerb_net* net) {
             net->param_slots[p + ".conv2.weight"].push_back({net->pc_rw2, (long long)oc * 256});
             net->param_slots[p + ".conv2.bias"].push_back({net->pc_rb2, oc});
         }
-        std::vector<float> w1t(512 * 256), b1f(256), w2t(256 * 16, 0.f), b2f(16, 0.f);
-        for (int o = 0; o < 256; ++o) {
-            for (int c = 0; c < 512; ++c) w1t[(size_t)c * 256 + o] = w1->data[(size_t)o * 512 + c] * f2.scale[o];
-            b1f[o] = b1->data[o] * f2.scale[o] + f2.shift[o];
-        }
-        for (int o = 0; o < oc; ++o) {
-            for (int c = 0; c < 256; ++c) w2t[(size_t)c * 16 + o] = w2->data[(size_t)o * 256 + c];
-            b2f[o] = b2->data[o];
-        }
+        std::vector<float> w1t, b1f, w2t, b2f;
+        cerb_host_pack_patch_class(w1->data.data(), b1->data.data(), f2.scale.data(), f2.shift.data(), w2->data.data(), b2->data.data(), oc, &w1t, &b1f, &w2t, &b2f);
         if (upload(net, f1.scale, &net->pc_bn1s) || upload(net, f1.shift, &net->pc_bn1b) || upload(net, w1t, &net->pc_w1t) ||
             upload(net, b1f, &net->pc_b1) || upload(net, w2t, &net->pc_w2t) || upload(net, b2f, &net->pc_b2))
             return 1;

@@ -350,6 +350,11 @@ struct cerb_net {
 static const int kLayers[4] = {3, 4, 6, 3};            // ResNet34 (models/backbone/resnet.py:273-286)
 static const int kFilters[5] = {64, 64, 128, 256, 512};
 void cerb_host_pack_conv(const float* w, int cout, int cin, int ks, int chunk, std::vector<float>* out);   // [cout][cin][ks][ks] -> conv_igemm.hip's stream
+void cerb_host_pack_stem(const float* w, const float* scale, std::vector<float>* out);                      // [64][3][7][7] x scale[64] -> stem_conv7x7_kernel's stream
+void cerb_host_pack_head(const float* w1, const float* b1, const float* scale, const float* shift, const float* w2, const float* b2, int out_ch,
+                         std::vector<float>* w1p, std::vector<float>* b1p, std::vector<float>* w2p, std::vector<float>* b2p, std::vector<float>* w2q);
+void cerb_host_pack_patch_class(const float* w1, const float* b1, const float* scale2, const float* shift2, const float* w2, const float* b2, int out_ch,
+                                std::vector<float>* w1t, std::vector<float>* b1f, std::vector<float>* w2t, std::vector<float>* b2f);
 void cerb_host_pack_wino(const float* w, int cout, int cin, std::vector<float>* out);                        // F(2x2,3x3) transform in conv_wino.hip's layout
 void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out);         // F(4x4,3x3) transform; layout 0 = conv_wino4 / 4p, 1 = conv_wino4b
 int prof_begin(cerb_net* net, const std::string& name, const std::string& kernel, double flops, hipStream_t st);  // per-launch records (cerb_net_profile_*)

@@ -1,6 +1,7 @@
 // dev_entry.hip -- test-only entry layer, linked into libcerberus_hip_dev.so ONLY (cerberus_amd/build.py: DEV_ONLY_SOURCES).  The backward kernels of
 // the training step are reachable in the product only through cerb_net_train_grads; these thin wrappers let tests/test_kernel_parity_gpu.py call one
-// launcher of cerb_net.h at a time, on raw device pointers, and compare it with a float64 reference of the same operation (tests/kernel_refs.py).
+// launcher of cerb_net.h at a time, on raw device pointers, and compare it with a float64 reference of the same operation (tests/kernel_refs.py);
+// the cerb_devfwd_* entries do the same for the forward path (convolutions, stem, output heads, Patch-Class, decoder entry, pool, layout).
 // No logic beyond argument checks: every wrapper returns the launcher's hipError_t as an int (0 = hipSuccess, 1 = hipErrorInvalidValue for a bad
 // argument).  Not part of the boundary: include/cerberus_hip.h declares none of this and libcerberus_hip.so exports none of it (tests/test_abi.py).
 #include "cerb_net.h"
@@ -278,6 +279,181 @@ int cerb_devfwd_maxpool(const float* in, float* out, int N, int H, int W, int C,
 int cerb_devfwd_planar_to_nhwc(const float* in, float* out, int N, int H, int W, int C, void* st) {
     DEV_NEED(in && out && N > 0);
     return (int)cerb_launch_planar_to_nhwc(in, out, N, H, W, C, (hipStream_t)st);
+}
+
+// ---- what lies between the convolutions and the user (tests/test_net_kernels_parity_gpu.py): stem, output heads, Patch-Class, the decoder entry with
+// a region of interest.  Weights arrive RAW, as the state dict holds them, and are packed here by the functions cerb_net_finalize packs with ---------
+// stem: tiles uint8 [N][H][W][3] or tiles_f32 (exactly one); w_raw DEVICE [64][3][7][7]; scale / shift HOST [64].  host_pack = 0: cerb_launch_pack_stem
+// (a training handle's packer: no scale, so scale must be 1), 1: cerb_host_pack_stem
+int cerb_devfwd_stem(const unsigned char* tiles, const float* tiles_f32, const float* w_raw, const float* scale, const float* shift, int host_pack, float* out, int N,
+                     int H, int W, int relu, void* st) {
+    DEV_NEED((tiles != nullptr) != (tiles_f32 != nullptr) && w_raw && scale && shift && out && N > 0 && H > 0 && W > 0);
+    const hipStream_t s = (hipStream_t)st;
+    float *dw = nullptr, *db = nullptr;
+    hipError_t e = hipSuccess;
+    if (host_pack) {
+        std::vector<float> raw(64 * 147), wp;
+        DEV_NEED(hipMemcpy(raw.data(), w_raw, raw.size() * 4, hipMemcpyDeviceToHost) == hipSuccess);
+        cerb_host_pack_stem(raw.data(), scale, &wp);
+        DEV_NEED(devfwd_upload(wp, &dw) == 0);
+    } else {
+        for (int c = 0; c < 64; ++c) DEV_NEED(scale[c] == 1.f);
+        DEV_NEED(hipMalloc((void**)&dw, 7 * 12 * 2 * 64 * 4) == hipSuccess);
+        e = cerb_launch_pack_stem(w_raw, dw, s);
+    }
+    if (devfwd_upload(std::vector<float>(shift, shift + 64), &db) != 0) e = hipErrorOutOfMemory;
+    StemParams p;
+    memset(&p, 0, sizeof(p));
+    p.tiles = tiles; p.tiles_f32 = tiles_f32; p.wpack = dw; p.bias = db; p.out = out; p.N = N; p.H = H; p.W = W; p.relu = relu;
+    if (e == hipSuccess) e = cerb_launch_stem(p, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(dw);
+    (void)hipFree(db);
+    return (int)e;
+}
+
+// One head of cerb_devfwd_head.  HOST: w1 [96][64], b1 [96], scale / shift [96] (the folded BatchNorm), w2 [out_ch][96], b2 [out_ch]; everything from
+// `logits` on is a DEVICE pointer or null, with the meaning of HeadParams (cerb_common.h).
+struct DevHead {
+    const float *w1, *b1, *scale, *shift, *w2, *b2;
+    int out_ch, kind, crop_y0, crop_x0, out_h, out_w, roi, pad_;
+    float* logits;
+    float* out_inst;
+    unsigned char* out_type_u8;
+    long long* out_type_i64;
+    const long long* tile_off;
+    long long tile_stride, row_stride;
+    unsigned int* absmax_bits;
+};
+// launcher: 0 cerb_launch_head (one head, NHWC features), 1 cerb_launch_head_group with w2_44 = 0, 2 the same with w2_44 = 1.  feat: [N][H][W][64] NHWC, or
+// (feat_planar) a tile-planar tensor of cerb_devfwd_planar_elems(N, H, W, 64) floats.  The shape rules are cerb_net_create's.
+int cerb_devfwd_head(int launcher, const float* feat, int feat_planar, int N, int H, int W, const DevHead* heads, int n_heads, void* st) {
+    DEV_NEED(launcher >= 0 && launcher <= 2 && feat && heads && N > 0 && H > 0 && W > 0 && n_heads >= 1 && n_heads <= 8);
+    DEV_NEED(launcher != 0 || (n_heads == 1 && !feat_planar));
+    for (int i = 0; i < n_heads; ++i) {
+        const DevHead& h = heads[i];
+        DEV_NEED(h.w1 && h.b1 && h.scale && h.shift && h.w2 && h.b2 && h.out_ch >= 2 && h.out_ch <= 8 && (h.kind == 0 || h.kind == 1));
+        DEV_NEED(h.kind == 1 || h.out_ch == 2 || h.out_ch == 3);
+        DEV_NEED(h.crop_y0 >= 0 && h.crop_x0 >= 0 && h.out_h > 0 && h.out_w > 0 && h.crop_y0 + h.out_h <= H && h.crop_x0 + h.out_w <= W);
+        DEV_NEED(!(h.roi && h.logits) && (h.kind == 0 ? h.out_inst != nullptr : (h.out_type_u8 || h.out_type_i64)));
+    }
+    const hipStream_t s = (hipStream_t)st;
+    HeadParams hp[8];
+    std::vector<float*> owned;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n_heads && e == hipSuccess; ++i) {
+        const DevHead& h = heads[i];
+        std::vector<float> pk[5];
+        cerb_host_pack_head(h.w1, h.b1, h.scale, h.shift, h.w2, h.b2, h.out_ch, &pk[0], &pk[1], &pk[2], &pk[3], &pk[4]);
+        float* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        for (int k = 0; k < 5; ++k) {
+            if (devfwd_upload(pk[k], &d[k]) != 0) e = hipErrorOutOfMemory;
+            owned.push_back(d[k]);
+        }
+        HeadParams& p = hp[i];
+        memset(&p, 0, sizeof(p));
+        p.feat = feat; p.w1p = d[0]; p.b1 = d[1]; p.w2p = d[2]; p.b2 = d[3]; p.w2q = d[4];
+        p.N = N; p.H = H; p.W = W; p.out_ch = h.out_ch; p.kind = h.kind;
+        p.crop_y0 = h.crop_y0; p.crop_x0 = h.crop_x0; p.out_h = h.out_h; p.out_w = h.out_w; p.roi = h.roi;
+        p.logits = h.logits; p.out_inst = h.out_inst; p.out_type_u8 = h.out_type_u8; p.out_type_i64 = h.out_type_i64;
+        p.tile_off = h.tile_off; p.tile_stride = h.tile_stride; p.row_stride = h.row_stride; p.absmax_bits = h.absmax_bits;
+        p.feat_planar = feat_planar;
+        if (feat_planar) { p.pl_byp = cerb_planar_blocks(H); p.pl_bxp = cerb_planar_blocks(W); }
+    }
+    if (e == hipSuccess) e = launcher == 0 ? cerb_launch_head(hp[0], s) : cerb_launch_head_group(hp, n_heads, s, launcher == 2);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    for (float* q : owned) (void)hipFree(q);
+    return (int)e;
+}
+
+// Patch-Class: x4 DEVICE [N][Hf][Wf][512]; HOST bn1 scale / shift [512], w1 [256][512], b1 [256], bn2 scale / shift [256], w2 [out_ch][256], b2 [out_ch];
+// logits DEVICE [N][out_ch] or null; out DEVICE canvas or null, addressed like the heads'
+int cerb_devfwd_patch_class(const float* x4, const float* bn1_scale, const float* bn1_shift, const float* w1, const float* b1, const float* bn2_scale,
+                            const float* bn2_shift, const float* w2, const float* b2, int N, int Hf, int Wf, int out_ch, int out_h, int out_w, float* logits, float* out,
+                            const long long* tile_off, long long tile_stride, long long row_stride, void* st) {
+    DEV_NEED(x4 && bn1_scale && bn1_shift && w1 && b1 && bn2_scale && bn2_shift && w2 && b2 && N > 0 && Hf > 0 && Wf > 0 && out_ch >= 1 && out_ch <= 16);
+    DEV_NEED((logits || out) && (!out || (out_h > 0 && out_w > 0)));
+    const hipStream_t s = (hipStream_t)st;
+    std::vector<float> pk[4];
+    cerb_host_pack_patch_class(w1, b1, bn2_scale, bn2_shift, w2, b2, out_ch, &pk[0], &pk[1], &pk[2], &pk[3]);
+    float* d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4; ++k)
+        if (devfwd_upload(pk[k], &d[k]) != 0) e = hipErrorOutOfMemory;
+    if (devfwd_upload(std::vector<float>(bn1_scale, bn1_scale + 512), &d[4]) != 0) e = hipErrorOutOfMemory;
+    if (devfwd_upload(std::vector<float>(bn1_shift, bn1_shift + 512), &d[5]) != 0) e = hipErrorOutOfMemory;
+    PatchClassParams p;
+    memset(&p, 0, sizeof(p));
+    p.x4 = x4; p.bn1_s = d[4]; p.bn1_b = d[5]; p.w1t = d[0]; p.b1 = d[1]; p.w2t = d[2]; p.b2 = d[3];
+    p.N = N; p.Hf = Hf; p.Wf = Wf; p.out_ch = out_ch; p.out_h = out_h; p.out_w = out_w; p.logits = logits; p.out = out;
+    p.tile_off = tile_off; p.tile_stride = tile_stride; p.row_stride = row_stride;
+    if (e == hipSuccess) e = cerb_launch_patch_class(p, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    for (float* q : d) (void)hipFree(q);
+    return (int)e;
+}
+
+// the decoder entry with a region of interest: roi = four HOST ints (y0, y1, x0, x1) in output pixels, or null
+int cerb_devfwd_upsample2_add_roi(const float* skip, const float* prev, float* out, int G, int N, int H, int W, int C, long long prev_gs, const int* roi, void* st) {
+    DEV_NEED(skip && prev && out && G > 0 && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C % 4 == 0);
+    DEV_NEED(!roi || (roi[0] >= 0 && roi[0] <= roi[1] && roi[1] <= H && roi[2] >= 0 && roi[2] <= roi[3] && roi[3] <= W));
+    return (int)cerb_launch_upsample2_add(skip, prev, out, G, N, H, W, C, prev_gs, roi, (hipStream_t)st);
+}
+int cerb_devfwd_upsample2_add_planar_roi(const float* skip, const float* prev, float* out, int G, int N, int H, int W, int C, long long prev_gs, long long out_gs,
+                                         const int* roi, int prev_planar, void* st) {
+    DEV_NEED(skip && prev && out && G > 0 && N > 0 && H > 0 && W > 0 && out_gs >= cerb_planar_elems(N, H, W, C));
+    DEV_NEED(!roi || (roi[0] >= 0 && roi[0] <= roi[1] && roi[1] <= H && roi[2] >= 0 && roi[2] <= roi[3] && roi[3] <= W));
+    return (int)cerb_launch_upsample2_add_planar(skip, prev, out, G, N, H, W, C, prev_gs, out_gs, roi, prev_planar, (hipStream_t)st);
+}
+
+// ---- the fused output-head passes of the training step (head_train.hip; tests/test_head_train_parity_gpu.py), and the two separate passes they replaced --
+int cerb_dev_head_train_supported(long long rows, int cin, int chid, int out) { return cerb_head_train_supported(rows, cin, chid, out) ? 1 : 0; }
+// in_mean .. in_beta: the BatchNorm in front of the head, all four or none.  bn_part: [2048][96][2] doubles at most; *bn_blocks: rows of it written
+int cerb_dev_head_fwd1(const float* prev, const float* w1, const float* b1, float* hid, long long rows, double* bn_part, int* bn_blocks, const float* in_mean,
+                       const float* in_rstd, const float* in_gamma, const float* in_beta, void* st) {
+    DEV_NEED(prev && w1 && b1 && hid && rows > 0);
+    DEV_NEED((in_mean != nullptr) == (in_rstd != nullptr) && (in_mean != nullptr) == (in_gamma != nullptr) && (in_mean != nullptr) == (in_beta != nullptr));
+    const float* in_bn[4] = {in_mean, in_rstd, in_gamma, in_beta};
+    return (int)cerb_launch_head_fwd1(prev, w1, b1, hid, rows, bn_part, bn_blocks, (hipStream_t)st, in_mean ? in_bn : nullptr);
+}
+int cerb_dev_head_fwd2(const float* hid, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* w2, const float* b2, float* logits,
+                       long long rows, int out, void* st) {
+    DEV_NEED(hid && mean && rstd && gamma && beta && w2 && b2 && logits && rows > 0 && out > 0);
+    return (int)cerb_launch_head_fwd2(hid, mean, rstd, gamma, beta, w2, b2, logits, rows, out, (hipStream_t)st);
+}
+size_t cerb_dev_head_bwd_workspace_bytes(long long rows, int out) { return rows > 0 && out > 0 ? cerb_head_bwd_workspace_bytes(rows, out) : 0; }
+int cerb_dev_head_bwd1(const float* hid, const float* dlog, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* w2, float* dw2,
+                       float* db2, float* dgamma, float* dbeta, long long rows, int out, void* ws, void* st) {
+    DEV_NEED(hid && dlog && mean && rstd && gamma && beta && w2 && dw2 && db2 && dgamma && dbeta && ws && rows > 0 && rows % 16 == 0);
+    return (int)cerb_launch_head_bwd1(hid, dlog, mean, rstd, gamma, beta, w2, dw2, db2, dgamma, dbeta, rows, out, ws, (hipStream_t)st);
+}
+// in_part: [min(rows / 64, cerb_head_bwd2_blocks())][64][2] doubles; *in_blocks (optional) reports that row count
+int cerb_dev_head_bwd2(const float* hid, const float* dlog, const float* prev, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                       const float* dgamma, const float* dbeta, const float* w1, const float* w2, float* dprev, float* dw1, float* db1, long long rows, int out, int eval_mode,
+                       int assign, void* ws, const float* in_mean, const float* in_rstd, const float* in_gamma, const float* in_beta, double* in_part, int* in_blocks,
+                       void* st) {
+    DEV_NEED(hid && dlog && prev && mean && rstd && gamma && beta && dgamma && dbeta && w1 && w2 && dprev && dw1 && db1 && ws && rows > 0);
+    DEV_NEED((in_mean != nullptr) == (in_rstd != nullptr) && (in_mean != nullptr) == (in_gamma != nullptr) && (in_mean != nullptr) == (in_beta != nullptr));
+    DEV_NEED(!in_part || in_mean);
+    if (in_blocks) *in_blocks = (int)std::min<long long>(rows / 64, cerb_head_bwd2_blocks());
+    const float* in_bn[4] = {in_mean, in_rstd, in_gamma, in_beta};
+    return (int)cerb_launch_head_bwd2(hid, dlog, prev, mean, rstd, gamma, beta, dgamma, dbeta, w1, w2, dprev, dw1, db1, rows, out, eval_mode, assign, ws, (hipStream_t)st,
+                                      in_mean ? in_bn : nullptr, in_part);
+}
+// in_scale: null or [rows][cin] (a dropout mask times 1 / (1 - p), per row and channel).  bn_part: [2048][cout][2] doubles at most, or null; *bn_blocks: rows of
+// it written (0: the layer did not produce them)
+int cerb_dev_pointwise(const float* in, const float* w, const float* bias, float* out, long long rows, int cin, int cout, const float* in_scale, double* bn_part,
+                       int* bn_blocks, void* st) {
+    DEV_NEED(in && w && bias && out && rows > 0 && cin > 0 && cout > 0);
+    return (int)cerb_launch_pointwise(in, w, bias, out, rows, cin, cout, in_scale, (hipStream_t)st, bn_part, bn_blocks);
+}
+int cerb_dev_bn_apply(float* x, const float* src, const float* resid, long long group_stride, long long rows, int C, int groups, const float* mean, const float* rstd,
+                      const float* gamma, const float* beta, int relu, void* st) {
+    DEV_NEED(x && mean && rstd && gamma && beta && rows > 0 && C > 0 && groups > 0 && group_stride >= rows * C);
+    return (int)cerb_launch_bn_apply(x, src, resid, group_stride, rows, C, groups, mean, rstd, gamma, beta, relu, (hipStream_t)st);
 }
 
 }  // extern "C"

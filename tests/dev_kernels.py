@@ -1,5 +1,6 @@
 """ctypes bindings of the test-only entry layer of libcerberus_hip_dev.so (cerberus_amd/csrc/dev_entry.hip: cerb_dev_<kernel> wrappers over single
-launchers of cerb_net.h for the training backward, cerb_devfwd_<kernel> for the forward path: cerb_devfwd_conv drives any one forward convolution launcher)
+launchers of cerb_net.h for the training step, cerb_devfwd_<kernel> for the forward path: cerb_devfwd_conv drives any one forward convolution launcher,
+cerb_devfwd_stem / _head / _patch_class take raw weights and pack them as the handle does)
 and the helpers that lay tensors out as the kernels expect, the tile-planar layout included.  Developer code: it lives under tests/, and works only in the
 child process of a `dev_switches` test (CERB_DEV_LIB=1), where cerberus_amd loads the developers' library.
 
@@ -59,7 +60,36 @@ _SIGS = {
     "cerb_devfwd_conv": (_I, [_I] * 5 + [_P, _I, _I] + [_P] * 6 + [_I] * 7 + [_LL] * 5 + [C.POINTER(C.c_int)] + [_I] * 3 + [_P]),
     "cerb_devfwd_wino4b_packed": (_I, [_I] * 6),
     "cerb_devfwd_wino4b_bn_blocks": (_I, [_I] * 6),
+    # stem, output heads, Patch-Class, the decoder entry with a region (tests/test_net_kernels_parity_gpu.py)
+    "cerb_devfwd_stem": (_I, [_P] * 5 + [_I, _P] + [_I] * 4 + [_P]),
+    "cerb_devfwd_head": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P]),
+    "cerb_devfwd_patch_class": (_I, [_P] * 9 + [_I] * 6 + [_P] * 3 + [_LL, _LL, _P]),
+    "cerb_devfwd_upsample2_add_roi": (_I, [_P] * 3 + [_I] * 5 + [_LL, C.POINTER(C.c_int), _P]),
+    "cerb_devfwd_upsample2_add_planar_roi": (_I, [_P] * 3 + [_I] * 5 + [_LL, _LL, C.POINTER(C.c_int), _I, _P]),
+    # the training step's fused output-head passes and the separate passes beside them (tests/test_head_train_parity_gpu.py)
+    "cerb_dev_head_train_supported": (_I, [_LL, _I, _I, _I]),
+    "cerb_dev_head_fwd1": (_I, [_P] * 4 + [_LL, _P, C.POINTER(C.c_int)] + [_P] * 5),
+    "cerb_dev_head_fwd2": (_I, [_P] * 8 + [_LL, _I, _P]),
+    "cerb_dev_head_bwd_workspace_bytes": (_SZ, [_LL, _I]),
+    "cerb_dev_head_bwd1": (_I, [_P] * 11 + [_LL, _I, _P, _P]),
+    "cerb_dev_head_bwd2": (_I, [_P] * 14 + [_LL, _I, _I, _I] + [_P] * 6 + [C.POINTER(C.c_int), _P]),
+    "cerb_dev_pointwise": (_I, [_P] * 4 + [_LL, _I, _I, _P, _P, C.POINTER(C.c_int), _P]),
+    "cerb_dev_bn_apply": (_I, [_P] * 3 + [_LL, _LL, _I, _I] + [_P] * 4 + [_I, _P]),
 }
+
+
+class DevHead(C.Structure):
+    """one head of cerb_devfwd_head (dev_entry.hip: struct DevHead); the first six are HOST float arrays, the pointers from `logits` on DEVICE ones"""
+    _fields_ = [(n, _P) for n in ("w1", "b1", "scale", "shift", "w2", "b2")] + [
+        (n, _I) for n in ("out_ch", "kind", "crop_y0", "crop_x0", "out_h", "out_w", "roi", "pad_")] + [
+        ("logits", _P), ("out_inst", _P), ("out_type_u8", _P), ("out_type_i64", _P), ("tile_off", _P), ("tile_stride", _LL), ("row_stride", _LL),
+        ("absmax_bits", _P)]
+
+
+def hptr(t):
+    """host pointer of a contiguous CPU tensor (the caller keeps the tensor alive across the call)"""
+    assert not t.is_cuda and t.is_contiguous()
+    return C.c_void_p(t.data_ptr())
 ENTRIES = sorted(_SIGS)
 _lib = None
 

@@ -6,7 +6,9 @@ Activations are NHWC with a leading group axis [G][N][H][W][C], weights [G][Cout
 Two references are written by hand: wgrad_wino_formula (the F(4x4,3x3) Winograd-domain weight gradient, the second yardstick of that kernel) and
 dilate2; tests/test_kernel_refs.py ties both to autograd on the host.  The forward convolutions (tests/test_conv_forward_parity_gpu.py) have conv_forward
 (F.conv2d + bias + residual + ReLU, the decoder entry in front of it) and wino_forward_formula, the F(2x2) / F(4x4) algorithm of the Winograd kernels
-evaluated plainly: the yardstick of those kernels, tied to conv2d in the same host test."""
+evaluated plainly: the yardstick of those kernels, tied to conv2d in the same host test.  The stem, the output heads, Patch-Class (its crop a real Python
+slice) and the heads' training passes (tests/test_net_kernels_parity_gpu.py, tests/test_head_train_parity_gpu.py) are plain torch expressions under
+autograd, tied to the torch.nn module chains in the same host test."""
 import torch
 import torch.nn.functional as F
 
@@ -232,3 +234,110 @@ def dilate2(dy):
     d = torch.zeros(n, 2 * h, 2 * w, c, dtype=dy.dtype)
     d[:, ::2, ::2, :] = dy
     return d
+
+
+# ---- between the convolutions and the user: stem, output heads, Patch-Class (tests/test_net_kernels_parity_gpu.py) ---------------------------------
+def stem_forward(tiles, w, scale, shift, relu, dt):
+    """tiles [N][H][W][3] (uint8 or float pixel values), w [64][3][7][7], scale / shift [64] (the folded BatchNorm) -> [N][H][W][64]:
+    conv2d(tiles / 255, w * scale, shift, padding = 3), then ReLU as asked"""
+    x = (tiles.permute(0, 3, 1, 2).to(dt) / 255).contiguous()
+    y = F.conv2d(x, w.to(dt) * scale.to(dt).view(64, 1, 1, 1), shift.to(dt), padding=3)
+    return (torch.relu(y) if relu else y).permute(0, 2, 3, 1).contiguous()
+
+
+def top2_margin(logits):
+    """logits [..., C] -> the two largest classes [..., 2] and the gap between their logits (softmax is monotone: the argmax of the probabilities is that of
+    the logits, and how close a decision is shows in the logits)"""
+    v, i = logits.topk(2, dim=-1)
+    return i, v[..., 0] - v[..., 1]
+
+
+def head_forward(feat, w1, b1, scale, shift, w2, b2, dt):
+    """feat [N][H][W][64]; w1 [96][64], b1, scale / shift [96] (the BatchNorm behind the first 1x1, folded), w2 [out][96], b2 [out] ->
+    dict(logits [N][H][W][out], prob = softmax, inst = prob[..., 1:], type = argmax, top2 [..., 2], margin)"""
+    hid = torch.relu((feat.to(dt) @ w1.to(dt).t() + b1.to(dt)) * scale.to(dt) + shift.to(dt))
+    logits = hid @ w2.to(dt).t() + b2.to(dt)
+    prob = torch.softmax(logits, -1)
+    top2, margin = top2_margin(logits)
+    return dict(logits=logits, prob=prob, inst=prob[..., 1:], type=prob.argmax(-1), top2=top2, margin=margin)
+
+
+def patch_class_crop(x):
+    """x [N][Hf][Wf][C] -> the window Patch-Class pools: the centre crop to 9 x 9 as the Python slice x[h0 : h0 + 9] with h0 = int((H - 9) * 0.5) (a negative
+    start counts from the end, a stop past the end is clipped: slicing does both), applied only when BOTH sides differ from 9"""
+    H, W = x.shape[1], x.shape[2]
+    if H != 9 and W != 9:
+        h0, w0 = int((H - 9) * 0.5), int((W - 9) * 0.5)
+        x = x[:, h0:h0 + 9, w0:w0 + 9]
+    return x
+
+
+def patch_class_forward(x4, bn1_scale, bn1_shift, w1, b1, bn2_scale, bn2_shift, w2, b2, dt, crop=patch_class_crop):
+    """x4 [N][Hf][Wf][512]: crop -> average pool -> BN1 -> ReLU -> 1x1 512->256 -> BN2 -> ReLU -> 1x1 256->out (the BatchNorms as scale / shift).
+    -> dict(logits [N][out], cls = argmax(softmax), top2, margin)"""
+    v = crop(x4.to(dt)).mean((1, 2))
+    v = torch.relu(v * bn1_scale.to(dt) + bn1_shift.to(dt))
+    h = torch.relu((v @ w1.to(dt).t() + b1.to(dt)) * bn2_scale.to(dt) + bn2_shift.to(dt))
+    logits = h @ w2.to(dt).t() + b2.to(dt)
+    if logits.shape[-1] > 1:
+        top2, margin = top2_margin(logits)
+    else:
+        top2, margin = torch.zeros(logits.shape[0], 2, dtype=torch.long), torch.full((logits.shape[0],), float("inf"), dtype=dt)
+    return dict(logits=logits, cls=torch.softmax(logits, -1).argmax(-1), top2=top2, margin=margin, v=v, h=h)
+
+
+# ---- the output heads of the training step (tests/test_head_train_parity_gpu.py) -------------------------------------------------------------------
+def bn_const(y, mean, rstd, gamma, beta, dt):
+    """(y - mean) rstd gamma + beta with the statistics as constants"""
+    return (y.to(dt) - mean.to(dt)) * rstd.to(dt) * gamma.to(dt) + beta.to(dt)
+
+
+def head_train_forward(prev, w1, b1, gamma, beta, w2, b2, dt, in_bn=None, hid=None, stats=None, eps=1e-5):
+    """prev [rows][64] -> p = relu(bn_in(prev)) when in_bn = (mean, rstd, gamma, beta) is given, else prev; hid = p W1^T + b1 (or the `hid` handed in: a
+    leaf, as for the kernels that take it as an input); z = relu(batch_norm(hid)) with batch statistics, or with stats = (mean, rstd) as constants
+    (eval mode); logits = z W2^T + b2.  Returns a dict of the tensors; p, hid (when handed in), w1, b1, gamma, beta, w2, b2 are autograd leaves."""
+    t = dict()
+    leaf = lambda v: v.detach().to(dt).clone().requires_grad_(True)
+    t["w1"], t["b1"], t["gamma"], t["beta"], t["w2"], t["b2"] = [leaf(v) for v in (w1, b1, gamma, beta, w2, b2)]
+    p = prev.to(dt) if in_bn is None else torch.relu(bn_const(prev, *in_bn, dt))
+    t["p"] = leaf(p)
+    t["hid_of_p"] = t["p"] @ t["w1"].t() + t["b1"]
+    t["hid"] = t["hid_of_p"] if hid is None else leaf(hid)
+    if stats is None:
+        bn = F.batch_norm(t["hid"], None, None, t["gamma"], t["beta"], training=True, eps=eps)
+    else:
+        bn = (t["hid"] - stats[0].to(dt)) * stats[1].to(dt) * t["gamma"] + t["beta"]   # (tests/test_kernel_refs.py: == BatchNorm2d in eval mode)
+    t["bn"] = bn
+    t["z"] = torch.relu(bn)
+    t["logits"] = t["z"] @ t["w2"].t() + t["b2"]
+    return t
+
+
+def head_train_backward(t, dlog, dt, prev=None, in_bn=None):
+    """autograd over head_train_forward(hid = a leaf): -> dict(dhid, dw2, db2, dgamma, dbeta, dprev = dhid W1 (the gradient with respect to p, NOT the raw
+    prev), dw1, db1) and, with prev / in_bn, in_part = (sum dz, sum dz xhat) of the BatchNorm in front, dz = dprev where relu(bn_in(prev)) > 0"""
+    t["logits"].backward(dlog.to(dt))
+    dhid = t["hid"].grad
+    if t["hid"] is t["hid_of_p"]:
+        raise ValueError("hand `hid` to head_train_forward: the backward kernels take it as an input")
+    t["hid_of_p"].backward(dhid)
+    g = dict(dhid=dhid, dw2=t["w2"].grad, db2=t["b2"].grad, dgamma=t["gamma"].grad, dbeta=t["beta"].grad, dprev=t["p"].grad, dw1=t["w1"].grad, db1=t["b1"].grad)
+    if in_bn is not None:
+        mean, rstd = in_bn[0].to(dt), in_bn[1].to(dt)
+        dz = g["dprev"] * (bn_const(prev, *in_bn, dt) > 0).to(dt)
+        g["in_part"] = torch.stack([dz.sum(0), (dz * (prev.to(dt) - mean) * rstd).sum(0)], -1)
+    return g
+
+
+def pointwise_forward(x, w, bias, in_scale, dt):
+    """(x * in_scale) @ w^T + bias on [rows][cin]; in_scale [rows][cin] (a dropout mask times 1 / (1 - p), per row and channel) or None"""
+    xs = x.to(dt) if in_scale is None else x.to(dt) * in_scale.to(dt)
+    return xs @ w.to(dt).t() + bias.to(dt)
+
+
+def bn_apply(src, resid, mean, rstd, gamma, beta, relu, dt):
+    """src [G][rows][C], statistics and affine [G][C]: relu?((src - mean) rstd gamma + beta (+ resid))"""
+    v = (src.to(dt) - mean.to(dt).unsqueeze(1)) * (rstd.to(dt) * gamma.to(dt)).unsqueeze(1) + beta.to(dt).unsqueeze(1)
+    if resid is not None:
+        v = v + resid.to(dt)
+    return torch.relu(v) if relu else v
