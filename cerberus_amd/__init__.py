@@ -7,14 +7,19 @@ Host mirrors of the reference interface (same names / argument meaning):
   cerberus_amd.tile / cerberus_amd.wsi              <- reference infer/tile.py, infer/wsi.py (geometry + stitching)
   cerberus_amd.targets.gen_targets (+ _batch)       <- reference loader/targets.py:185-244 with loader/augs.py fix_mirror_padding
   cerberus_amd.valid_stats.ValidStats / valid_step_stats / validate <- reference models/run_desc.py:606-747 (ProcStepRawOutput) and :505-565
+  cerberus_amd.augs.sample_params / augment_batch / train_batch <- reference loader/augs.py (the lambdas) and the affine / flip / crop steps around them
 All arithmetic runs in libcerberus_hip.so (include/cerberus_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"
 
 
-def __getattr__(name):  # cerberus_amd.ValidStats / valid_step_stats / validate, imported on first use (the package import stays torch-free)
+def __getattr__(name):  # cerberus_amd.ValidStats / valid_step_stats / validate / sample_params / ..., imported on first use (the package import stays torch-free)
     if name in ("ValidStats", "valid_step_stats", "validate"):
         from . import valid_stats
 
         return getattr(valid_stats, name)
+    if name in ("sample_params", "augment_batch", "train_batch", "TRAIN_POLICY"):
+        from . import augs
+
+        return getattr(augs, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

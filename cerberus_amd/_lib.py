@@ -17,6 +17,8 @@ EXPORTS = [
     "cerb_jpeg_workspace_bytes", "cerb_jpeg_decode_stream", "cerb_jpeg_read_tiles", "cerb_jpeg_decode_window",
     "cerb_tissue_workspace_bytes", "cerb_tissue_hed", "cerb_tissue_entropy", "cerb_tissue_histogram", "cerb_tissue_threshold", "cerb_tissue_morphology",
     "cerb_inst_areas", "cerb_inst_pairs_workspace_bytes", "cerb_inst_pairs", "cerb_inst_pairs_compact", "cerb_inst_pair_stats_workspace_bytes", "cerb_inst_pair_stats",
+    "cerb_aug_warp", "cerb_aug_gaussian_blur", "cerb_aug_median_blur", "cerb_aug_gaussian_noise", "cerb_aug_brightness", "cerb_aug_saturation", "cerb_aug_hue",
+    "cerb_aug_contrast", "cerb_aug_channel_sums",
 ]
 
 
@@ -207,6 +209,14 @@ def lib():
     L.cerb_inst_pair_stats_workspace_bytes.restype = C.c_size_t
     L.cerb_inst_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.cerb_aug_warp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_aug_gaussian_blur.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cerb_aug_median_blur.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_aug_gaussian_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for f in (L.cerb_aug_brightness, L.cerb_aug_saturation, L.cerb_aug_hue):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_aug_contrast.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cerb_aug_channel_sums.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "libcerberus_hip.so")
 LIB_DEV = os.path.join(HERE, "libcerberus_hip_dev.so")
 LIB_HOST = os.path.join(HERE, "libcerberus_host.so")
 HOST_SOURCES = ["host_codecs.c"]
-SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip", "conv_wino4p.hip", "net_kernels.hip", "postproc.hip", "slide_kernels.hip", "train_kernels.hip", "head_train.hip", "conv_wgrad.hip", "conv_wgrad_wino.hip", "pack_kernels.hip", "targets.hip", "valid_stats.hip", "jpeg_kernels.hip", "tissue_mask.hip", "inst_metrics.hip", "cerb_api.hip", "cerb_train.hip"]
+SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip", "conv_wino4p.hip", "net_kernels.hip", "postproc.hip", "slide_kernels.hip", "train_kernels.hip", "head_train.hip", "conv_wgrad.hip", "conv_wgrad_wino.hip", "pack_kernels.hip", "targets.hip", "valid_stats.hip", "jpeg_kernels.hip", "tissue_mask.hip", "inst_metrics.hip", "augs.hip", "cerb_api.hip", "cerb_train.hip"]
 # The translation units that read developer A/B switches (cerb_common.h: cerb_dev_getenv).  The product library compiles them WITHOUT the switches
 # (every one folds to its default); the same units compiled with -DCERB_DEV_SWITCHES, linked with the other units' objects, make
 # libcerberus_hip_dev.so -- loaded only by the A/B tests' child processes (CERB_DEV_LIB=1, cerberus_amd/_lib.py).
@@ -32,7 +32,9 @@ EXTRA_FLAGS = {"conv_wino4.hip": ["-mllvm", "-pragma-unroll-threshold=1000000", 
                # 144 accumulators fit the AccVGPR half: the default AGPR form (the VGPR-form rewrite pass of ROCm 7.2 crashes on this kernel)
                "conv_wino4b.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
                # accumulators pinned by hand (inline-asm matrix instructions with "a" / "v" constraints): no allocator flag needed
-               "conv_wino4p.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"]}
+               "conv_wino4p.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+               # the fp64 definitions of include/cerberus_hip.h round every product and sum on its own (numpy's arithmetic): no fused multiply-add
+               "augs.hip": ["-ffp-contract=off"]}
 
 
 def _stale(target, deps):

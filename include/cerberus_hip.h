@@ -26,7 +26,7 @@ extern "C" {
 typedef struct cerb_net cerb_net;
 #define CERB_ERR_ALLOC 2
 
-int cerb_version(void);
+int cerb_version(void); /* 2: with the training augmentations (the cerb_aug entries below); 1 before */
 const char* cerb_last_error(void);
 
 /* ---- network construction: replaces create_model / NetDesc.__init__ (models/net_desc.py:23-103,203) ----------
@@ -561,6 +561,69 @@ size_t cerb_inst_pair_stats_workspace_bytes(int n_true, int n_pred);
 int cerb_inst_pair_stats(const long long* keys, const long long* counts, long long n_pairs, const long long* true_area, int n_true,
                          const long long* pred_area, int n_pred, const int32_t* true_type, const int32_t* pred_type, int cls,
                          long long* summary, double* sum_iou, void* ws, size_t ws_bytes, void* hip_stream);
+
+/* ---- training augmentations: the shape and input augmentations in front of gen_targets (loader/augs.py lambdas + affine / flip / crop) --------------
+ * The host draws every random number (cerberus_amd/augs.py: sample_params) and uploads a few numbers per sample; every call below is a pure function
+ * of (input, per-sample parameter arrays), runs the whole batch in ONE launch on hip_stream, allocates nothing and does not synchronise.  Images are
+ * uint8 [n][h][w][3] (RGB), annotations int32 [n][h][w][c], both dense; parameter arrays are device arrays of n entries.  The definitions are this
+ * project's own, in integers and float64 (binary64, every product, quotient and sum rounded on its own -- no fused multiply-add): bit parity with
+ * OpenCV / imgaug is NOT claimed; where OpenCV documents its 8-bit behaviour (H in 0..179, the sigma = 0 Gaussian tables, the
+ * fixed-point grey weights) the definitions follow it, pinned by tests/golden/augs_documented.json.
+ * Every call refuses (error, no launch): a null pointer, n outside 1..65535, an empty image, a side above 16384.  The stencil calls (warp, the two
+ * blurs) are out of place and refuse overlapping src / dst; the point-wise calls (noise, colour) accept dst == src and refuse any other overlap.
+ *
+ * cerb_aug_warp: affine + centre crop + flips of image and annotation in one nearest-neighbour gather.
+ *   maps: int64 [n][6] = (A, B, C, D, E, F) in Q16.  For the output pixel (u, v) = (column, row), in 64-bit integers with an arithmetic shift:
+ *       xs = (A u + B v + C + 32768) >> 16,   ys = (D u + E v + F + 32768) >> 16
+ *   out[v][u] = src[ys][xs] (all channels of both arrays) when 0 <= xs < src_w and 0 <= ys < src_h, else 0.  Either array (with its output) may be NULL.
+ *   The host composes the map (cerberus_amd/augs.py: compose_map): the forward map in (x, y) pixel coordinates of the src_w x src_h canvas is
+ *       M = T(c + t) R(theta) Shear_x(phi) S(sx, sy) T(-c),  c = ((src_w - 1) / 2, (src_h - 1) / 2),
+ *       R = [cos -sin; sin cos], Shear_x = [1 tan(phi); 0 1], S = diag(sx, sy), T = translation, multiplied left to right as 3 x 3 float64 matrices;
+ *   with M = [a b c; d e f; 0 0 1] and det = a e - b d its inverse is [e/det  -b/det  (b f - c e)/det;  -d/det  a/det  (c d - a f)/det]; each of the six
+ *   entries m becomes int(rint(m * 65536)).  Then, exactly in integers: the centre crop to out_h x out_w with (oy, ox) = ((src_h - out_h) / 2,
+ *   (src_w - out_w) / 2) (floor): C += A ox + B oy, F += D ox + E oy; a left-right flip of the OUTPUT: C += A (out_w - 1), F += D (out_w - 1), A = -A,
+ *   D = -D; an up-down flip: C += B (out_h - 1), F += E (out_h - 1), B = -B, E = -E.
+ *
+ * cerb_aug_gaussian_blur: per sample (kx[i], ky[i]), each in {1, 3, 5}: weights [1], [1 2 1] (sum 4), [1 4 6 4 1] (sum 16) -- OpenCV's tables for
+ *   sigma = 0 --, borders replicate (the coordinate is clamped), out = (sum_y sum_x wy wx p + half) >> shift with shift = log2(sum_x sum_y) and
+ *   half = 2^(shift-1) (0 when shift = 0): round half up, in integers.  kx = ky = 1 is a copy.
+ * cerb_aug_median_blur: per sample k[i] in {1, 3, 5}: per channel the median (element k k / 2 of the sorted k x k window), borders replicate.
+ *   For both blurs a size of 0 (or any value outside {1, 3, 5}) leaves that sample of dst UNWRITTEN: augment_batch runs the blur, the median and the
+ *   noise call on the same src / dst pair and each sample is written by exactly one of them.
+ *
+ * cerb_aug_gaussian_noise: per sample sigma[i] (float64), per_channel[i] (int32, 0 / non-zero), key[i] (uint64).  For pixel index q = v w + u of the
+ *   sample, Philox4x32-10 (Salmon et al. 2011; multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85) with key (key & 0xffffffff, key >> 32) and
+ *   counter (q & 0xffffffff, q >> 32, 0, 0) gives r0..r3;  u1 = (r0 + 1) 2^-32, u2 = r1 2^-32, u3 = (r2 + 1) 2^-32, u4 = r3 2^-32;
+ *   z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2), z2 = sqrt(-2 ln u3) cos(2 pi u4), with 2 pi = 6.283185307179586.
+ *   per_channel: channels (R, G, B) get (z0, z1, z2); otherwise all three get z0.  out = clip(floor(p + sigma z + 0.5), 0, 255) in float64.
+ *   sigma = 0 is a copy.  A sigma that is not finite leaves that sample of dst UNWRITTEN.  (ln / cos / sin come from the device's math library:
+ *   a result may differ from another library's where p + sigma z + 0.5 lies within rounding of an integer -- tests/test_augs_gpu.py states the rule.)
+ *
+ * Colour, one call per operation, value[i] float64 per sample; a value that is not finite SKIPS the sample (copied when dst != src).  p = a channel
+ * value, trunc(clip(x, 0, 255)) = the float64 -> uint8 store of numpy after np.clip:
+ *   cerb_aug_brightness  out = trunc(clip(p + value, 0, 255)).
+ *   cerb_aug_saturation  g = (4899 R + 9617 G + 1868 B + 8192) >> 14 (OpenCV's 8-bit grey), s = 1 + value, out = trunc(clip(p s + g (1 - s), 0, 255)).
+ *   cerb_aug_hue         RGB -> HSV in integers: V = max, d = V - min, S = floor((510 d + V) / (2 V)) (round-half-up of 255 d / V; 0 when V = 0);
+ *                        H = 0 when d = 0, else with hnum = G - B if V = R, else (B - R) + 2 d if V = G, else (R - G) + 4 d:
+ *                        H = floor((60 hnum + d) / (2 d)), plus 180 if negative, minus 180 if >= 180 (H in 0..179).
+ *                        Shift: x = H + value; r = fmod(x, 180), plus 180 if r < 0 (the divisor's sign, as numpy's %); H' = trunc(r).
+ *                        HSV -> RGB: s = S / 255, v = V, hh = H' / 30, i = floor(hh), f = hh - i, p = v (1 - s), q = v (1 - s f), t = v (1 - s (1 - f));
+ *                        (R, G, B) = (v,t,p), (q,v,p), (p,v,t), (p,q,v), (t,p,v), (v,p,q) for i mod 6 = 0..5; each rounded half to even to uint8.
+ *   cerb_aug_contrast    mean_c = sums[i][c] / (h w) in float64 (sums: int64 [n][3] from cerb_aug_channel_sums of the same src);
+ *                        out = trunc(clip(p value + mean_c (1 - value), 0, 255)).  The reference's add_to_contrast returns its INPUT
+ *                        (loader/augs.py:71-78 clips `img`, not `ret`): cerberus_amd.augs mirrors that by default and calls this only on request.
+ *   cerb_aug_channel_sums  sums[i][c] = the exact integer sum of channel c of sample i (the call clears sums; integer partial sums, 64-bit integer atomics). */
+int cerb_aug_warp(const uint8_t* img, const int32_t* ann, int n, int src_h, int src_w, int ann_c, const int64_t* maps, uint8_t* img_out,
+                  int32_t* ann_out, int out_h, int out_w, void* hip_stream);
+int cerb_aug_gaussian_blur(const uint8_t* src, uint8_t* dst, int n, int h, int w, const int32_t* kx, const int32_t* ky, void* hip_stream);
+int cerb_aug_median_blur(const uint8_t* src, uint8_t* dst, int n, int h, int w, const int32_t* k, void* hip_stream);
+int cerb_aug_gaussian_noise(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* sigma, const int32_t* per_channel,
+                            const uint64_t* key, void* hip_stream);
+int cerb_aug_brightness(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, void* hip_stream);
+int cerb_aug_saturation(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, void* hip_stream);
+int cerb_aug_hue(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, void* hip_stream);
+int cerb_aug_contrast(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, const int64_t* sums, void* hip_stream);
+int cerb_aug_channel_sums(const uint8_t* src, int n, int h, int w, int64_t* sums, void* hip_stream);
 
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
