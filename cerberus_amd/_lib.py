@@ -19,6 +19,7 @@ EXPORTS = [
     "cerb_inst_areas", "cerb_inst_pairs_workspace_bytes", "cerb_inst_pairs", "cerb_inst_pairs_compact", "cerb_inst_pair_stats_workspace_bytes", "cerb_inst_pair_stats",
     "cerb_aug_warp", "cerb_aug_gaussian_blur", "cerb_aug_median_blur", "cerb_aug_gaussian_noise", "cerb_aug_brightness", "cerb_aug_saturation", "cerb_aug_hue",
     "cerb_aug_contrast", "cerb_aug_channel_sums",
+    "cerb_overlay_workspace_bytes", "cerb_overlay_clear", "cerb_overlay_stamp", "cerb_overlay_resolve",
 ]
 
 
@@ -217,6 +218,13 @@ def lib():
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_aug_contrast.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cerb_aug_channel_sums.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.cerb_overlay_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.cerb_overlay_workspace_bytes.restype = C.c_size_t
+    L.cerb_overlay_clear.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_overlay_stamp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_longlong,
+                                     C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_overlay_resolve.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_longlong, C.c_int, C.c_int, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

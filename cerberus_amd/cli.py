@@ -19,6 +19,9 @@ TILE_OPTIONS = _COMMON + [
     ("--output_dir", True, "output/", "where <tissue>_mat/, pclass_mat/ and overlay/ are written"),
     ("--patch_input_shape", True, "448", "network input window (square)"),
     ("--patch_output_shape", True, "144", "centre crop kept from every window (square)"),
+    ("--overlay", True, "host", "(not in the reference) host | device: where overlay/<name>.jpg is drawn -- host: PIL on the writer threads, contour by contour; "
+                                "device: the contour rasteriser (cerb_overlay_*, cerberus_amd/viz.py) with the x2 up-scaling fused, the writer threads only "
+                                "encode the JPEG.  The two strokes differ in a cosmetic share of the painted pixels; the .mat files are the same"),
 ]
 WSI_OPTIONS = _COMMON + [
     ("--batch_size", True, "30", "patches per forward"),
@@ -50,7 +53,7 @@ WSI_OPTIONS = _COMMON + [
     ("--auto_mask_ds", True, "16", "(not in the reference) with --auto_mask: the thumbnail is the slide at 1/<n> of the processing resolution"),
 ]
 # WSI_OPTIONS is pinned, entry by entry, by tests/test_tissue_mask_host.py and is closed: every NEW run_infer_wsi.py option goes into WSI_MODEL_OPTIONS
-# below (appended at its end), and run_infer_wsi.py parses WSI_ALL_OPTIONS = WSI_OPTIONS + WSI_MODEL_OPTIONS.
+# below (appended at its end) or into WSI_OUTPUT_OPTIONS further down, and run_infer_wsi.py parses all three tables (WSI_DRIVER_OPTIONS).
 WSI_MODEL_OPTIONS = [
     ("--eroded_maps", False, False, "(not in the reference's command line) run a model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, PostProcInstErodedMap) "
                                     "on slides: one-channel canvases, the eroded labelling inside the band / halo / ownership protocol; without the flag such a "
@@ -58,6 +61,16 @@ WSI_MODEL_OPTIONS = [
                                     "streaming are refused"),
 ]
 WSI_ALL_OPTIONS = WSI_OPTIONS + WSI_MODEL_OPTIONS
+# WSI_ALL_OPTIONS is pinned as well (tests/test_eroded_wsi_host.py): options about what the driver WRITES go here, and run_infer_wsi.py parses
+# WSI_DRIVER_OPTIONS = WSI_ALL_OPTIONS + WSI_OUTPUT_OPTIONS.
+WSI_OUTPUT_OPTIONS = [
+    ("--save_overlay", False, False, "(not in the reference) write <output_dir>/overlay/<slide>.jpg: the slide at 1/--overlay_ds of the processing resolution with every "
+                                     "instance of dat/<slide>.dat drawn on it on the device (line width 2; the reference's visualize_instances_dict, "
+                                     "misc/viz_utils.py:150-184); needs a slide with a reader (not a `synthetic:` spec)"),
+    ("--overlay_ds", True, "8", "(not in the reference) with --save_overlay: the picture is the slide at 1/<n> of the processing resolution, n a whole number >= 1; "
+                                "a picture side above 32768 is refused"),
+]
+WSI_DRIVER_OPTIONS = WSI_ALL_OPTIONS + WSI_OUTPUT_OPTIONS
 # compute_stats.py (not a driver of the reference's command line: its compute_stats.py is a script with paths edited in place)
 STATS_OPTIONS = [
     ("--gpu", True, "0", "GPU id, exported as HIP_VISIBLE_DEVICES"),

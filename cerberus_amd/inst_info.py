@@ -63,6 +63,22 @@ def info_from_table(tab, cnts, pts, offs, has_type, ds_factor=1.0, flat_box=Fals
     return info
 
 
+def majority_type(tab):
+    """The `type` of every row of a cerb_inst_table array [n, 16], kept or not: info_from_table's vote rule on its own (columns 8..15 are the votes per
+    class) -- the class with the most votes, ties towards the smaller class id; background (0) gives way to the runner-up when that one has a vote.
+    -> int64 [n].  (tests/test_overlay_host.py holds it equal to info_from_table's values.)"""
+    votes = np.asarray(tab)[:, 8:16].astype(np.int64)
+    n = votes.shape[0]
+    if n == 0:
+        return np.zeros(0, np.int64)
+    rows = np.arange(n)
+    first = np.argmax(votes, axis=1)  # (the first maximum: the smaller class id on a tie)
+    rest = votes.copy()
+    rest[rows, first] = -1
+    runner = np.argmax(rest, axis=1)
+    return np.where((first == 0) & (votes[rows, runner] > 0), runner, first).astype(np.int64)
+
+
 def _shift_points(pts, cnts, offs, origin):
     """pts + origin[i] for the points of instance i when the point list is not simply the concatenation of the instances' runs."""
     out = np.array(pts, copy=True)

@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from .net_desc import create_model
-from .postproc import get_inst_info_dict, mask_lumen_by_gland, postproc_device, postproc_eroded_device
+from .postproc import (get_inst_info_dict, info_from_table, inst_contours_device, inst_table_device, mask_lumen_by_gland, postproc_device,
+                       postproc_eroded_device)
 from .run_desc import infer_step
 
 CONTOUR_CODES = ("IP-ERODED-CONTOUR-3", "IP-ERODED-CONTOUR-11")  # -> PostProcInstErodedContourMap (infer/tile.py:35-40): three-class INST heads
@@ -343,7 +344,11 @@ class InferManager(object):
                         yield f, im, r
                     cur, n_patch, n_px = [], 0, 0
 
-        def write_outputs(base, img, mats, info_all, pclass_np):
+        # overlay="device" (run_infer_tile.py --overlay=device): the picture is drawn on the device from the arrays the dictionary is built from
+        # (cerberus_amd.viz.overlay_from_parts, x2 up-scaling fused) and arrives at the writer finished -- only the JPEG encoding is left to the pool
+        device_overlay = getattr(self, "overlay", "host") == "device"
+
+        def write_outputs(base, img, mats, info_all, pclass_np, picture=None):
             for tissue, mat in mats:
                 os.makedirs("%s/%s_mat/" % (self.output_dir, tissue.lower()), exist_ok=True)
                 sio.savemat("%s/%s_mat/%s.mat" % (self.output_dir, tissue.lower(), base), mat)
@@ -351,7 +356,9 @@ class InferManager(object):
             from .viz import up2_nearest, visualize_instances_dict_orig
 
             os.makedirs("%s/overlay/" % self.output_dir, exist_ok=True)
-            Image.fromarray(visualize_instances_dict_orig(up2_nearest(img), info_all)).save("%s/overlay/%s.jpg" % (self.output_dir, base))
+            if picture is None:
+                picture = visualize_instances_dict_orig(up2_nearest(img), info_all)
+            Image.fromarray(picture).save("%s/overlay/%s.jpg" % (self.output_dir, base))
             if pclass_np is not None:
                 os.makedirs("%s/pclass_mat/" % self.output_dir, exist_ok=True)
                 sio.savemat("%s/pclass_mat/%s.mat" % (self.output_dir, base), {"pclass": pclass_np})
@@ -365,7 +372,7 @@ class InferManager(object):
             def up2(t):  # cv2.resize(fx=2, fy=2, INTER_NEAREST) of an integer map, on the device
                 return t.repeat_interleave(2, dim=0).repeat_interleave(2, dim=1).contiguous()
 
-            info_all, mats = {}, []
+            info_all, mats, parts = {}, [], []
             for tissue, lab in res["inst"].items():
                 lab_np = lab.cpu().numpy()
                 tmap = res["type"].get(tissue)
@@ -373,18 +380,31 @@ class InferManager(object):
                 if tissue != "Lumen" and tmap is not None:
                     prev_type = up2(tmap)
                 # instance table on the GPU; the reference re-uses the previous tissue's type map for Lumen (infer/tile.py:196-202)
-                info = get_inst_info_dict(up2(lab), prev_type)
-                info_all[tissue] = info
+                if device_overlay:  # get_inst_info_dict's own steps, keeping the arrays: the dictionary and the picture come from the same ones
+                    lab2 = up2(lab)
+                    tab_dev = inst_table_device(lab2, prev_type)
+                    cnts, pts, offs = inst_contours_device(lab2, tab_dev)
+                    tab = tab_dev.cpu().numpy()
+                    info = info_from_table(tab, cnts, pts, offs, prev_type is not None)
+                    parts.append((tissue, tab, cnts, pts, offs, prev_type is not None, 1.0))
+                else:
+                    info = get_inst_info_dict(up2(lab), prev_type)
+                    info_all[tissue] = info
                 mat = {"inst_map": lab_np.astype(np.float64) if tissue != "Nuclei" else lab_np,
                        "type": [d.get("type", -1) for d in info.values()], "id": list(info.keys())}
                 if tmap_np is not None:
                     mat["type_map"] = tmap_np.astype(np.float32)
                 mats.append((tissue, mat))
             pclass_np = res["pclass"].cpu().numpy() if res["pclass"] is not None else None
+            picture = None
+            if device_overlay:
+                from .viz import overlay_from_parts
+
+                picture = overlay_from_parts(img, parts, up=2).cpu().numpy()
             if writers is None:
-                write_outputs(base, img, mats, info_all, pclass_np)
+                write_outputs(base, img, mats, info_all, pclass_np, picture)
             else:
-                pending.append(writers.submit(write_outputs, base, img, mats, info_all, pclass_np))
+                pending.append(writers.submit(write_outputs, base, img, mats, info_all, pclass_np, picture))
                 while len(pending) > 4 * n_io:  # bounded: a tile's maps stay in RAM until its files are written
                     pending.popleft().result()
         while pending:

@@ -1,6 +1,7 @@
 """Overlay rendering of the tile CLI (reference misc/viz_utils.py:187-214 `visualize_instances_dict_orig`,
-called at infer/tile.py:251-257).  Pure host code: contours come from the GPU (cerb_inst_contour_*), drawing is PIL
-(`cv2.drawContours` is not available in this image; line rasterisation may differ from OpenCV's by a pixel -- cosmetic)."""
+called at infer/tile.py:251-257).  The first half is pure host code: contours come from the GPU (cerb_inst_contour_*), drawing is PIL
+(`cv2.drawContours` is not available in this image; line rasterisation may differ from OpenCV's by a pixel -- cosmetic).  The second half draws
+the same pictures, and the slide overlay of misc/viz_utils.py:150-184, on the device (cerb_overlay_*)."""
 
 import numpy as np
 
@@ -41,3 +42,192 @@ def up2_nearest(img):
     """cv2.resize(img, (0, 0), fx=2, fy=2, interpolation=INTER_NEAREST) (infer/tile.py:254)."""
     a = np.asarray(img)
     return np.repeat(np.repeat(a, 2, axis=0), 2, axis=1)
+
+
+# ---- the same pictures drawn on the device (cerb_overlay_*: include/cerberus_hip.h "instance overlays", DESIGN.md par.4.14) -------------------------
+# The stroke is the project's own integer definition (round caps and joints, exact), not PIL's and not OpenCV's: the two differ from it in a share of
+# the painted pixels that is cosmetic and unpinned.  Nothing below draws on the host, and nothing falls back to the functions above.
+DRAW_ORDER = ("Gland", "Lumen", "Nuclei")
+OVERLAY_MAX_SIDE = 32768
+
+
+def colour_word(rgb):
+    """(R, G, B) -> the uint32 word R | G << 8 | B << 16 of cerb_overlay_resolve."""
+    r, g, b = (int(c) & 255 for c in tuple(rgb)[:3])
+    return r | (g << 8) | (b << 16)
+
+
+def contour_colours(tissue, tab, has_type, viz_info=None):
+    """uint32 colour word per row of a cerb_inst_table array: the type colour where the instance has a type (inst_info.majority_type; a type the
+    tissue has no colour for falls back as in visualize_instances_dict_orig), else the tissue's instance colour."""
+    from .inst_info import majority_type
+
+    vi = (DEFAULT_VIZ_INFO if viz_info is None else viz_info)[tissue.lower()]
+    n = int(np.asarray(tab).shape[0])
+    if not has_type:
+        return np.full(n, colour_word(vi["inst_colour"]), np.uint32)
+    lut = np.array([colour_word(vi["type_colour"].get(t, vi["inst_colour"])) for t in range(8)], np.uint32)
+    return lut[majority_type(tab)]
+
+
+def _pack_dict(tissue, insts, vi, width=None):
+    """One tissue of an instance dictionary {id: {'contour': (K, 2) (x, y), 'type'?}} as a group of draw_contours_device (host arrays)."""
+    pts, cnts, cols = [], [], []
+    for info in insts.values():
+        contour = info.get("contour")
+        if contour is None or len(contour) < 2:
+            continue
+        c = np.asarray(contour).reshape(-1, 2)
+        pts.append(c.astype(np.int64))
+        cnts.append(c.shape[0])
+        cols.append(colour_word(vi["type_colour"].get(int(info["type"]), vi["inst_colour"]) if "type" in info else vi["inst_colour"]))
+    counts = np.asarray(cnts, np.int32)
+    return {"points": np.concatenate(pts) if pts else np.zeros((0, 2), np.int64), "offsets": np.cumsum(counts, dtype=np.int64) - counts, "counts": counts,
+            "colours": np.asarray(cols, np.uint32), "width": int(vi["line_width"] if width is None else width), "mul": 1, "div": 1, "origin": (0, 0)}
+
+
+def _group_to_device(g, dev):
+    """-> (points int32 [P, 2], offsets int64 [n], counts int32 [n], colours uint32-as-int32 [n]) on dev.  A run that leaves the point list draws nothing:
+    host arrays are checked (ValueError), device arrays get their count cleared on the device -- no host wait."""
+    import torch
+
+    def put(a, dt, shape):
+        if isinstance(a, torch.Tensor):
+            t = a.to(device=dev, dtype=dt)
+        else:
+            a = np.asarray(a)
+            if dt == torch.int32 and a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                raise ValueError("draw_contours_device: a value does not fit int32")
+            t = torch.from_numpy(np.ascontiguousarray(a.astype({torch.int32: np.int32, torch.int64: np.int64}[dt]))).to(dev)
+        return t.reshape(shape).contiguous()
+
+    pts, offs, cnts = put(g["points"], torch.int32, (-1, 2)), put(g["offsets"], torch.int64, (-1,)), put(g["counts"], torch.int32, (-1,))
+    col = g["colours"]
+    if isinstance(col, torch.Tensor):
+        col = col.to(device=dev).contiguous().view(torch.int32).reshape(-1)
+    else:
+        col = torch.from_numpy(np.ascontiguousarray(np.asarray(col, dtype=np.uint32)).view(np.int32)).to(dev).reshape(-1)
+    n = int(cnts.shape[0])
+    if int(offs.shape[0]) != n or int(col.shape[0]) != n:
+        raise ValueError("draw_contours_device: offsets, counts and colours must have one entry per contour")
+    if not any(isinstance(g[k], torch.Tensor) for k in ("points", "offsets", "counts")):
+        o, c = np.asarray(g["offsets"], dtype=np.int64).reshape(-1), np.maximum(np.asarray(g["counts"], dtype=np.int64).reshape(-1), 0)
+        if n and not bool(((o >= 0) & (o + c <= int(pts.shape[0]))).all()):
+            raise ValueError("draw_contours_device: a contour's run of points leaves the point list")
+    else:
+        inside = (offs >= 0) & (offs + cnts.clamp(min=0) <= int(pts.shape[0]))
+        cnts = torch.where(inside, cnts, torch.zeros_like(cnts))
+    if pts.shape[0] == 0:
+        pts = torch.zeros((1, 2), dtype=torch.int32, device=dev)
+    return pts, offs, cnts, col
+
+
+def draw_contours_device(image, groups, up=1):
+    """image: uint8 [H, W, 3] RGB, numpy or CUDA; groups: a list of {'points' [P, 2] (x, y), 'offsets' [n], 'counts' [n], 'colours' uint32 [n]
+    (R | G << 8 | B << 16), 'width' 1..255, 'mul' 1..16, 'div' 1..4096, 'origin' (x, y)}, arrays numpy or CUDA.  Contour i of a group is the closed
+    polygon through points[offsets[i] : offsets[i] + counts[i]], each point taken through (p mul - origin) / div (toward zero).  Groups are drawn in
+    list order and contours in array order, later over earlier.  -> CUDA uint8 [H up, W up, 3]: the image up-scaled (nearest) with the strokes on it.
+    One clear, one stamp per group and one resolve on the current stream, with no host wait in between."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+
+    L = _lib.lib()
+    if isinstance(image, torch.Tensor):
+        if not image.is_cuda:
+            image = image.cuda()
+        src = image
+    else:
+        src = torch.from_numpy(np.ascontiguousarray(np.asarray(image))).cuda()
+    if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError("draw_contours_device: the image must be uint8 [H, W, 3], got %s %s" % (src.dtype, tuple(src.shape)))
+    if src.stride(2) != 1 or src.stride(1) != 3:
+        src = src.contiguous()
+    dev = src.device
+    h, w, up = int(src.shape[0]), int(src.shape[1]), int(up)
+    oh, ow = h * up, w * up
+    if not (1 <= up <= 8) or min(h, w) < 1 or max(oh, ow) > OVERLAY_MAX_SIDE:
+        raise ValueError("draw_contours_device: up must be 1..8 and the picture's sides 1..%d, got a %d x %d image with up=%r" % (OVERLAY_MAX_SIDE, h, w, up))
+    packed = [_group_to_device(g, dev) for g in groups]
+    total = sum(int(p[2].shape[0]) for p in packed)
+    colours = torch.cat([p[3] for p in packed]) if total else torch.zeros(1, dtype=torch.int32, device=dev)
+    ws_bytes = int(L.cerb_overlay_workspace_bytes(oh, ow))
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=dev)
+    dst = torch.empty((oh, ow, 3), dtype=torch.uint8, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        _lib.check(L.cerb_overlay_clear(ws.data_ptr(), ws_bytes, oh, ow, stream))
+        first = 0
+        for g, (pts, offs, cnts, _) in zip(groups, packed):
+            n = int(cnts.shape[0])
+            if n:
+                ox, oy = (int(v) for v in g.get("origin", (0, 0)))
+                _lib.check(L.cerb_overlay_stamp(pts.data_ptr(), offs.data_ptr(), cnts.data_ptr(), n, int(g.get("mul", 1)), int(g.get("div", 1)), ox, oy,
+                                                int(g["width"]), first, ws.data_ptr(), ws_bytes, oh, ow, stream))
+            first += n
+        _lib.check(L.cerb_overlay_resolve(src.data_ptr(), int(src.stride(0)), h, w, up, colours.data_ptr(), total, ws.data_ptr(), ws_bytes,
+                                          dst.data_ptr(), int(dst.stride(0)), oh, ow, stream))
+    return dst
+
+
+def pack_parts(parts, extra=None, viz_info=None, ds=1, origin=(0, 0), line_width=None):
+    """The groups draw_contours_device takes (host arrays) for the instance arrays of a slide or tile.  parts: [(tissue, tab, cnts, pts, offs,
+    has_type, ds_factor[, per-instance origin])] as collect_wsi_inst_arrays / build_from_parts have them; extra: {tissue: {key: ready dictionary}}
+    (the per-region dictionaries of masked slides, already in the dictionary's coordinates).  Draw order Gland, Lumen, Nuclei whatever order the
+    parts come in; instances info_from_table drops (area == 0, fewer than 3 points) get a count of 0; a part whose ds_factor is 0.5 is drawn with
+    mul = 2, and per-instance tile origins are added here, on the host, as info_from_table adds them (np.round(p / ds_factor) + origin)."""
+    from .inst_info import _shift_points
+
+    viz_info = DEFAULT_VIZ_INFO if viz_info is None else viz_info
+    ox, oy = (int(v) for v in origin)
+    groups = []
+    for tissue in DRAW_ORDER:
+        vi = viz_info[tissue.lower()]
+        width = int(vi["line_width"] if line_width is None else line_width)
+        for part in parts or ():
+            if part[0] != tissue:
+                continue
+            _, tab, cnts, pts, offs, has_type, ds_factor = part[:7]
+            inst_origin = part[7] if len(part) > 7 else None
+            tab, cnts, offs = np.asarray(tab), np.asarray(cnts), np.asarray(offs, dtype=np.int64)
+            n = int(tab.shape[0])
+            if n == 0:
+                continue
+            counts = np.where((tab[:, 0] > 0) & (cnts >= 3), cnts, 0).astype(np.int32)
+            pts = np.asarray(pts).reshape(-1, 2)
+            mul = 1
+            if float(ds_factor) == 0.5 and inst_origin is None:
+                mul = 2  # np.round(p / 0.5) of an integer is 2 p: multiplied on the device
+            elif float(ds_factor) != 1.0:
+                pts = np.round(pts / float(ds_factor)).astype("int")
+            if inst_origin is not None:
+                org, c64 = np.asarray(inst_origin, dtype=np.int64).reshape(n, 2), cnts.astype(np.int64)
+                if len(pts) == int(c64.sum()) and np.array_equal(offs, np.cumsum(c64) - c64):  # the runs are the list, in order: one repeat
+                    pts = pts.astype(np.int64) + np.repeat(org, c64, axis=0)
+                else:
+                    pts = _shift_points(pts.astype(np.int64), cnts, offs, org)
+            groups.append({"points": pts, "offsets": offs, "counts": counts, "colours": contour_colours(tissue, tab, bool(has_type), viz_info),
+                           "width": width, "mul": mul, "div": int(ds), "origin": (ox, oy)})
+        if extra and extra.get(tissue):
+            g = _pack_dict(tissue, extra[tissue], vi, width)
+            g["counts"] = np.where(g["counts"] >= 3, g["counts"], 0).astype(np.int32)
+            g["div"], g["origin"] = int(ds), (ox, oy)
+            groups.append(g)
+    return groups
+
+
+def overlay_from_parts(image, parts, extra=None, viz_info=None, up=1, ds=1, origin=(0, 0), line_width=None):
+    """The overlay of a tile or slide from its instance ARRAYS, without a dictionary: image (uint8 [H, W, 3], numpy or CUDA) up-scaled by `up` with
+    every instance of `parts` and `extra` (see pack_parts) drawn on it at (p - origin) / ds, p in the instance dictionary's coordinates.
+    line_width=None: the tissue's viz_info width.  -> CUDA uint8 [H up, W up, 3]."""
+    return draw_contours_device(image, pack_parts(parts, extra, viz_info, ds, origin, line_width), up)
+
+
+def visualize_instances_dict_device(input_image, inst_dict_, viz_info=None):
+    """visualize_instances_dict_orig for callers who hold a dictionary, drawn on the device: same arguments, same kind of result (a new uint8 RGB
+    numpy array), same tissue order, colours and widths; the stroke is the integer definition of include/cerberus_hip.h instead of PIL's."""
+    viz_info = DEFAULT_VIZ_INFO if viz_info is None else viz_info
+    groups = [_pack_dict(t, inst_dict_[t], viz_info[t.lower()]) for t in DRAW_ORDER if t in inst_dict_]
+    return draw_contours_device(np.ascontiguousarray(np.asarray(input_image).astype(np.uint8)), groups, 1).cpu().numpy()

@@ -26,7 +26,7 @@ extern "C" {
 typedef struct cerb_net cerb_net;
 #define CERB_ERR_ALLOC 2
 
-int cerb_version(void); /* 2: with the training augmentations (the cerb_aug entries below); 1 before */
+int cerb_version(void); /* 3: with the instance overlays (the cerb_overlay entries below); 2: with the training augmentations (cerb_aug); 1 before */
 const char* cerb_last_error(void);
 
 /* ---- network construction: replaces create_model / NetDesc.__init__ (models/net_desc.py:23-103,203) ----------
@@ -624,6 +624,39 @@ int cerb_aug_saturation(const uint8_t* src, uint8_t* dst, int n, int h, int w, c
 int cerb_aug_hue(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, void* hip_stream);
 int cerb_aug_contrast(const uint8_t* src, uint8_t* dst, int n, int h, int w, const double* value, const int64_t* sums, void* hip_stream);
 int cerb_aug_channel_sums(const uint8_t* src, int n, int h, int w, int64_t* sums, void* hip_stream);
+
+/* ---- instance overlays: closed contours drawn over a picture (misc/viz_utils.py:150-214; cerberus_amd/viz.py) ---------------------------------------
+ * The project's own definition, in integers throughout: cv2.drawContours is not pinned.  Three calls on hip_stream, none of which
+ * allocates or synchronises: clear the priority plane, stamp groups of contours into it, resolve it into the picture.
+ *
+ * Covered pixel.  A pixel (x, y) is covered by the segment a -> b drawn with width w (1..255) iff the distance from its centre to the segment is at
+ * most w / 2.  With v = b - a, u = p - a, vv = v.v, t = u.v, c = ux vy - uy vx (int64):
+ *     vv == 0 or t <= 0 :  covered iff 4 (u.u) <= w^2
+ *     t >= vv           :  covered iff 4 |p - b|^2 <= w^2
+ *     otherwise         :  covered iff |c| <= isqrt(floor(w^2 vv / 4)),   isqrt = the exact integer square root
+ *   A round-capped, round-jointed stroke.  A zero-length segment is a disk: 1 pixel for w = 1, the 5-pixel plus for w = 2, the full 3 x 3 for w = 3.
+ *   An EVEN width paints w + 1 pixels across an axis-aligned line (the integers with |c| <= w / 2), an odd width w.
+ * Contours.  Contour i has counts[i] points, points[offsets[i] .. offsets[i] + counts[i]) (int32 (x, y) pairs), and is closed: segment k runs from
+ *   point k to point (k + 1) mod count.  A count of 0 (or below) draws nothing, 1 a disk, 2 one capsule.  Offsets need not be contiguous or ordered.
+ * Point transform, per call, in int64: q = p mul - (org_x, org_y), p' = q / div truncated toward zero (C division; numpy's astype("int") of the
+ *   quotient).  mul in 1..16, div in 1..4096, |org| <= 2^40.  A contour with ANY transformed coordinate outside [-2^20, 2^20] is skipped as a whole.
+ *   Every segment's box is expanded by (w + 1) / 2 and clipped to the image: no loop is longer than the image.
+ * Painter's order.  The workspace is a plane of uint32, one per output pixel: the largest ORDINAL of the contours covering the pixel, 0 = none, written
+ *   with an integer atomic max -- the result does not depend on the execution order.  Contour i of a stamp call has ordinal first_ordinal + i + 1
+ *   (contours with no points keep theirs): first_ordinal = the number of contours stamped since the clear, so that groups with different widths share
+ *   one plane and a later contour overwrites an earlier one.  first_ordinal + n must stay below 2^32 - 1.
+ * Resolve.  dst[y][x] = colours[prio - 1] where prio = plane[y][x] is in 1..n_total, and src[y / up][x / up] elsewhere: the nearest-neighbour
+ *   up-scaling (up in 1..8, out_h == src_h up, out_w == src_w up) is part of the pass.  Both images are uint8 RGB with row strides in bytes (bytes
+ *   between rows are not touched); a colour is the uint32 word R | G << 8 | B << 16.  dst must not overlap src.
+ * Refusals (an error, no launch, nothing written): a null pointer (colours may be NULL when n_total is 0), a side outside 1..32768, width / mul / div /
+ *   up out of range, a workspace smaller than cerb_overlay_workspace_bytes(out_h, out_w) = 4 out_h out_w (0 for a refused size) or not 4-byte aligned,
+ *   a negative n, a row stride shorter than its row. */
+size_t cerb_overlay_workspace_bytes(int out_h, int out_w);
+int cerb_overlay_clear(void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream);
+int cerb_overlay_stamp(const int32_t* points, const int64_t* offsets, const int32_t* counts, long long n, int mul, int div, long long org_x,
+                       long long org_y, int width, long long first_ordinal, void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream);
+int cerb_overlay_resolve(const uint8_t* src, long long src_row_stride, int src_h, int src_w, int up, const uint32_t* colours, long long n_total,
+                         const void* ws, size_t ws_bytes, uint8_t* dst, long long dst_row_stride, int out_h, int out_w, void* hip_stream);
 
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);

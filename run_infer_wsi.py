@@ -10,6 +10,8 @@ slide also gets `tissue/<slide>.mat` (infer/wsi.py:688-716).  `--auto_mask` make
 1/`--auto_mask_ds` of the processing resolution (the reference's get_tissue_mask, misc/utils.py:195-244); everything after it is the `--msk_dir` path.
 A model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, one canvas channel, PostProcInstErodedMap) is refused by name unless
 `--eroded_maps` is given; with it such heads get one-channel canvases and are labelled through the same bands (not with `--reference_tiling` for nuclei).
+`--save_overlay` also writes `overlay/<slide>.jpg`: the slide at 1/`--overlay_ds` with every instance of the dictionary drawn on it on the device
+(cerberus_amd/viz.py: overlay_from_parts; the reference's visualize_instances_dict, misc/viz_utils.py:150-184).
 
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N run_infer_wsi.py ...`; patch rows shard into one
 contiguous band per rank, inference needs no collective, post-processing is band-local (cerberus_amd/shard_postproc.py)."""
@@ -22,7 +24,7 @@ import time
 
 import numpy as np
 
-from cerberus_amd.cli import WSI_ALL_OPTIONS, parse, require_model
+from cerberus_amd.cli import WSI_DRIVER_OPTIONS, parse, require_model
 
 
 # largest map labelled in one call on one GPU (400 Mpx = 38 GB of workspace); larger slides are labelled in row bands (CERB_ONE_CALL_MPX moves the line)
@@ -115,10 +117,51 @@ def _check_auto_mask(args):
             raise ValueError("--auto_mask: %s is a synthetic slide spec (`synthetic:<H>x<W>:<seed>`): it has no reader to take a thumbnail from" % os.path.basename(p))
 
 
+OVERLAY_MAX_SIDE = 32768  # cerb_overlay_*: the largest picture side (include/cerberus_hip.h)
+
+
+def _thumb_hw(reader, proc_mpp, ds):
+    """(h, w) of cerberus_amd.tissue.thumbnail(reader, proc_mpp, "mpp", ds), from the slide's dimensions alone."""
+    tw, th = (max(1, int(v)) for v in reader.slide_dimensions(reader._scale(proc_mpp, "mpp") / float(ds), "baseline"))
+    return th, tw
+
+
+def _check_save_overlay(args):
+    """--save_overlay is refused, before a device is touched or a slide's pixels are read, where it cannot work: a divisor that is not a whole number
+    >= 1, a `synthetic:<H>x<W>:<seed>` spec (no reader to take the picture from), and a picture with a side above 32768 -- the message names the
+    smallest divisor that fits.  (Only the slides' headers are read here.)"""
+    if not args["--save_overlay"]:
+        return
+    try:
+        ds = int(args["--overlay_ds"])
+    except ValueError:
+        ds = 0
+    if ds < 1:
+        raise ValueError("--overlay_ds takes a whole number >= 1, got %r" % (args["--overlay_ds"],))
+    from cerberus_amd.reader import WSIReader
+
+    for p in _slide_list(args):
+        if os.path.splitext(p)[1].lower() == ".txt":
+            raise ValueError("--save_overlay: %s is a synthetic slide spec (`synthetic:<H>x<W>:<seed>`): it has no reader to take the picture from" % os.path.basename(p))
+        reader = WSIReader.open(input_img=p)
+        try:
+            if max(_thumb_hw(reader, float(args["--wsi_proc_mag"]), ds)) > OVERLAY_MAX_SIDE:
+                fit = ds + 1
+                while max(_thumb_hw(reader, float(args["--wsi_proc_mag"]), fit)) > OVERLAY_MAX_SIDE:
+                    fit += 1
+                raise ValueError("--save_overlay: at --overlay_ds=%d the picture of %s is %d x %d pixels, above %d a side; the smallest divisor that fits is "
+                                 "--overlay_ds=%d" % ((ds, os.path.basename(p)) + _thumb_hw(reader, float(args["--wsi_proc_mag"]), ds) + (OVERLAY_MAX_SIDE, fit)))
+        finally:
+            fh = getattr(reader, "fh", None)
+            if fh is not None:
+                fh.close()
+
+
 def main(argv=None):
-    args = parse("run_infer_wsi.py", WSI_ALL_OPTIONS, argv, version="CoBi Gland Inference")
+    args = parse("run_infer_wsi.py", WSI_DRIVER_OPTIONS, argv, version="CoBi Gland Inference")
     require_model(args)
     _check_auto_mask(args)
+    _check_save_overlay(args)
     if args["--jpeg_decode"] not in ("host", "device"):
         sys.exit("--jpeg_decode takes host or device, got %r" % args["--jpeg_decode"])
     if args["--jpeg_decode"] == "device":  # (before the ranks are started: they inherit it)
@@ -224,6 +267,7 @@ def main(argv=None):
         if min(H, W) < 4:  # (the quarter-resolution tissue map and the half-resolution gland maps have no pixels: the reference dies in cv2.resize there)
             raise ValueError("%s is %d x %d pixels at the processing resolution: nothing to segment" % (base, H, W))
         mask, sel, regions = None, None, None
+        thumb, thumb_ds = None, None  # the --auto_mask thumbnail, kept for --save_overlay when the divisor is the same
         if msk_dir or auto_mask:
             from cerberus_amd.tissue import TissueRegions, get_tissue_mask, load_mask, select_patches, thumbnail
             from cerberus_amd.wsi import SlideGeometry
@@ -234,6 +278,7 @@ def main(argv=None):
                 # every rank computes the mask from the same thumbnail with the same integer / table arithmetic: the same mask, no collective
                 t_m = time.perf_counter()
                 thumb = thumbnail(reader, float(args["--wsi_proc_mag"]), "mpp", int(args["--auto_mask_ds"]))
+                thumb_ds = int(args["--auto_mask_ds"])
                 try:
                     mask = get_tissue_mask(torch.from_numpy(thumb).cuda()).cpu().numpy()
                 except ValueError as e:  # nothing to threshold: skipped like a slide without a mask file under --msk_dir
@@ -505,6 +550,23 @@ def main(argv=None):
         if writer is not None:
             writer.join()
         writer = DatWriter.from_arrays(parts, meta, dat_path, extra=extra)
+        if args["--save_overlay"]:  # every instance that goes into the .dat, drawn on the device over the slide at 1 / --overlay_ds (misc/viz_utils.py:150-184)
+            from PIL import Image
+
+            from cerberus_amd.tissue import thumbnail as _thumbnail
+            from cerberus_amd.viz import overlay_from_parts
+
+            t_o = time.perf_counter()
+            ods = int(args["--overlay_ds"])
+            if thumb is None or thumb_ds != ods:
+                thumb = _thumbnail(reader, float(args["--wsi_proc_mag"]), "mpp", ods)
+            picture = overlay_from_parts(thumb, parts, extra=extra, ds=ods, line_width=2).cpu().numpy()
+            os.makedirs(os.path.join(out_dir, "overlay"), exist_ok=True)
+            Image.fromarray(picture).save(os.path.join(out_dir, "overlay", base + ".jpg"))
+            if log:
+                log.info("Overlay Time: {0} ({1} x {2} picture)".format(time.perf_counter() - t_o, picture.shape[0], picture.shape[1]))
+            picture = None
+        thumb = None
         t4 = time.perf_counter()
         print("%s: Inference Time: %.3f  Post Proc Time: %.3f  Instance Table Time: %.3f  (%.1f Mpx/s inference)" % (
             base, t1 - t0, t2 - t1, t4 - t3, H * W / (t1 - t0) / 1e6))
