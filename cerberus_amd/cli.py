@@ -22,6 +22,10 @@ TILE_OPTIONS = _COMMON + [
     ("--overlay", True, "host", "(not in the reference) host | device: where overlay/<name>.jpg is drawn -- host: PIL on the writer threads, contour by contour; "
                                 "device: the contour rasteriser (cerb_overlay_*, cerberus_amd/viz.py) with the x2 up-scaling fused, the writer threads only "
                                 "encode the JPEG.  The two strokes differ in a cosmetic share of the painted pixels; the .mat files are the same"),
+    ("--overlay_encode", True, "host", "(not in the reference) host | device: where overlay/<name>.jpg is JPEG-encoded -- host: PIL on the writer threads; device: with "
+                                       "--overlay=device only, the picture never leaves the device: colour conversion, DCT, Huffman coding and packing run in HIP "
+                                       "(cerb_jpeg_enc_*, cerberus_amd/jpeg_encode.py) and the writer threads receive the compressed bytes.  The same pixels "
+                                       "on decoding; the file has one restart interval per MCU row"),
 ]
 WSI_OPTIONS = _COMMON + [
     ("--batch_size", True, "30", "patches per forward"),
@@ -69,7 +73,18 @@ WSI_OUTPUT_OPTIONS = [
                                      "misc/viz_utils.py:150-184); needs a slide with a reader (not a `synthetic:` spec)"),
     ("--overlay_ds", True, "8", "(not in the reference) with --save_overlay: the picture is the slide at 1/<n> of the processing resolution, n a whole number >= 1; "
                                 "a picture side above 32768 is refused"),
+    ("--overlay_encode", True, "host", "(not in the reference) host | device, with --save_overlay only: where overlay/<slide>.jpg is JPEG-encoded -- host: the picture is "
+                                       "downloaded and PIL encodes it; device: it is encoded in HIP (cerb_jpeg_enc_*, cerberus_amd/jpeg_encode.py) and only the "
+                                       "compressed bytes are downloaded.  The same pixels on decoding; the file has one restart interval per MCU row"),
 ]
+
+
+def check_overlay_encode(args, drawn_on_device, needs):
+    """--overlay_encode=device encodes a picture that is already on the device: refused by name where there is none (ValueError naming both options)."""
+    if args["--overlay_encode"] not in ("host", "device"):
+        raise ValueError("--overlay_encode takes host or device, got %r" % (args["--overlay_encode"],))
+    if args["--overlay_encode"] == "device" and not drawn_on_device:
+        raise ValueError("--overlay_encode=device needs %s: the encoder takes the picture the device drew, and without it there is none" % needs)
 WSI_DRIVER_OPTIONS = WSI_ALL_OPTIONS + WSI_OUTPUT_OPTIONS
 # compute_stats.py (not a driver of the reference's command line: its compute_stats.py is a script with paths edited in place)
 STATS_OPTIONS = [

@@ -347,6 +347,28 @@ class InferManager(object):
         # overlay="device" (run_infer_tile.py --overlay=device): the picture is drawn on the device from the arrays the dictionary is built from
         # (cerberus_amd.viz.overlay_from_parts, x2 up-scaling fused) and arrives at the writer finished -- only the JPEG encoding is left to the pool
         device_overlay = getattr(self, "overlay", "host") == "device"
+        # overlay_encode="device" (--overlay_encode=device): the picture is not downloaded either -- it is JPEG-encoded where it was drawn
+        # (cerberus_amd.jpeg_encode) and the writer receives the handle of the queued encode: its one wait is for the compressed bytes.  An encoder
+        # serves one picture at a time, so a writer hands its encoder back when it has the bytes and the next picture of a fitting size takes it.
+        device_encode = getattr(self, "overlay_encode", "host") == "device"
+        if device_encode and not device_overlay:
+            raise ValueError("overlay_encode='device' needs overlay='device' (--overlay_encode=device needs --overlay=device)")
+        free_encoders = deque()
+
+        def queue_encode(picture):
+            from .jpeg_encode import Encoder
+
+            h, w = int(picture.shape[0]), int(picture.shape[1])
+            enc = None
+            for _ in range(len(free_encoders)):
+                cand = free_encoders.popleft()
+                if enc is None and cand.max_w >= w and cand.max_h >= h:
+                    enc = cand
+                else:
+                    free_encoders.append(cand)
+            if enc is None:
+                enc = Encoder(picture.device, w, h)
+            return enc, enc.encode(picture)
 
         def write_outputs(base, img, mats, info_all, pclass_np, picture=None):
             for tissue, mat in mats:
@@ -358,7 +380,12 @@ class InferManager(object):
             os.makedirs("%s/overlay/" % self.output_dir, exist_ok=True)
             if picture is None:
                 picture = visualize_instances_dict_orig(up2_nearest(img), info_all)
-            Image.fromarray(picture).save("%s/overlay/%s.jpg" % (self.output_dir, base))
+            if isinstance(picture, tuple):  # (encoder, handle of the queued encode)
+                with open("%s/overlay/%s.jpg" % (self.output_dir, base), "wb") as fh:
+                    fh.write(picture[1].bytes())
+                free_encoders.append(picture[0])
+            else:
+                Image.fromarray(picture).save("%s/overlay/%s.jpg" % (self.output_dir, base))
             if pclass_np is not None:
                 os.makedirs("%s/pclass_mat/" % self.output_dir, exist_ok=True)
                 sio.savemat("%s/pclass_mat/%s.mat" % (self.output_dir, base), {"pclass": pclass_np})
@@ -400,7 +427,8 @@ class InferManager(object):
             if device_overlay:
                 from .viz import overlay_from_parts
 
-                picture = overlay_from_parts(img, parts, up=2).cpu().numpy()
+                picture = overlay_from_parts(img, parts, up=2)
+                picture = queue_encode(picture) if device_encode else picture.cpu().numpy()
             if writers is None:
                 write_outputs(base, img, mats, info_all, pclass_np, picture)
             else:

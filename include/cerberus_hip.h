@@ -523,6 +523,48 @@ int cerb_jpeg_read_tiles(int fd, int n_tiles, const int64_t* offsets, const int6
 int cerb_jpeg_decode_window(const void* dev_buf, size_t dev_bytes, int n_tiles, int tile_w, int tile_h, uint8_t* scratch, size_t scratch_bytes,
                             uint8_t* dst, long long dst_row_stride, int x0, int y0, int x1, int y1, void* hip_stream);
 
+/* ---- JPEG encoding of a picture on the device: colour / DCT / Huffman / packing (cerberus_amd/jpeg_encode.py) -----------------------------------
+ * The mirror of "JPEG tiles" above: a uint8 RGB picture that lives on the device becomes the entropy-coded scan of a baseline JPEG file, and only the
+ * compressed bytes cross to the host (csrc/jpeg_encode.hip; the headers around the scan are written in Python).  Not in the reference, which hands
+ * whole pictures to cv2 / PIL on the host.  Equal to PIL's Image.save(format="JPEG", quality=q, subsampling=s) -- libjpeg's integer forward path, Annex-K
+ * Huffman tables, optimize=False -- coefficient for coefficient, and to save(..., restart_marker_rows=1) byte for byte in the scan.
+ *   cerb_jpeg_enc_workspace_bytes(w, h, subsampling, which): which = 0 the workspace of cerb_jpeg_enc_coefs (the component planes), 1 the bytes of the
+ *                           coefficients, 2 the workspace of cerb_jpeg_enc_scan, 3 the most a scan of this picture can take (scan_cap that never
+ *                           truncates).  0 for a size or a subsampling the calls refuse.
+ *   cerb_jpeg_enc_coefs     src: uint8 RGB, rows row_stride bytes apart (>= 3 w; any alignment: a view into a larger picture is fine).  coefs: int16,
+ *                           16-byte aligned, IN THE DECODER'S LAYOUT: per component a raster of (mcu_rows v) x (mcu_cols h) blocks of 64 in natural
+ *                           order -- what cerb_jpeg_decode_window reads.  qtables: uint16 [2][64] on the device, the luminance and the chrominance
+ *                           table in natural order, or null.  workspace: 8-byte aligned.  Two launches.
+ *   cerb_jpeg_enc_scan      coefs -> scan_out[0 .. *scan_len_dev): every MCU row is one restart interval (DRI = MCU columns), RSTm (m = row mod 8)
+ *                           between the intervals, none after the last.  workspace: 128-byte aligned.  *scan_len_dev (int64 on the device) is the
+ *                           scan's full length; bytes at or past scan_cap are not written, so a caller that gave less than
+ *                           cerb_jpeg_enc_workspace_bytes(.., 3) compares the two.  One memset and four launches.
+ * Both refuse BEFORE any launch (1, cerb_last_error names the argument): w or h outside 1 .. 32768, quality outside 1 .. 100, subsampling other than
+ * 0 (4:4:4) / 2 (4:2:0), a workspace smaller than cerb_jpeg_enc_workspace_bytes says.  They queue on hip_stream, allocate nothing, do not synchronise.
+ * Capacity: with the Annex-K tables a block takes at most 11 + 11 bits of DC and 63 x (16 + 10) bits of AC = 1660 bits < 208 bytes, so an interval of n
+ * blocks has a slot of 208 n bytes (+ 8, rounded to 128) before stuffing and at most twice that + 2 in the scan: no 8-bit picture overruns at any
+ * quality, and every store is checked against the slot / scan_cap all the same.
+ * Arithmetic (all integers, >> arithmetic, products in 64 bits):
+ *   colour  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *           Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *   edges   libjpeg's order: columns are replicated at FULL resolution out to the MCU grid (8 for 4:4:4, 16 for 4:2:0); rows are replicated at full
+ *           resolution only up to an even count (4:2:0, odd h), the component is down-sampled, and ITS last row is replicated down to the MCU grid.
+ *   4:2:0   out[r][c] = (p[2r][2c] + p[2r][2c+1] + p[2r+1][2c] + p[2r+1][2c+1] + bias) >> 2, bias 1 for even c and 2 for odd c.
+ *   DCT     jfdctint ("islow") on sample - 128, the 13-bit constants of the inverse one.  Pass 1 along the rows: outputs 0 and 4 are (t10 +- t11) << 2,
+ *           the others (x + 1024) >> 11.  Pass 2 down the columns: outputs 0 and 4 (x + 2) >> 2, the others (x + 16384) >> 15.  8 x the DCT.
+ *   tables  Annex K scaled as libjpeg does: scale = 5000 / q (q < 50) else 200 - 2 q; entry = clamp((base scale + 50) / 100, 1, 255).
+ *   quantisation  sign(c) ((|c| + (8 Q >> 1)) / (8 Q)).
+ *   dummy blocks  4:2:0 only: a Y block of an MCU that lies wholly beyond Y's own grid of ceil(h / 8) x ceil(w / 8) blocks has no AC terms and the
+ *           (quantised) DC of the block before it in the MCU's order; in a bottom row of dummies both blocks take the MCU's top-right block's.
+ *   coding  baseline Huffman, Annex-K tables, zig-zag order, MCUs interleaved (4:2:0: four Y blocks in raster order, Cb, Cr); DC difference per
+ *           component, predictors reset at every interval; category = bit length of |d|, magnitude bits d or d - 1 (d < 0); run / size symbols with ZRL
+ *           for 16 zeros and EOB for a zero tail; every interval padded to a byte with 1-bits; FF followed by 00. */
+size_t cerb_jpeg_enc_workspace_bytes(int w, int h, int subsampling, int which);
+int cerb_jpeg_enc_coefs(const uint8_t* src, long long row_stride, int w, int h, int quality, int subsampling, int16_t* coefs, uint16_t* qtables,
+                        void* workspace, size_t ws_bytes, void* hip_stream);
+int cerb_jpeg_enc_scan(const int16_t* coefs, int w, int h, int subsampling, void* workspace, size_t ws_bytes, uint8_t* scan_out, size_t scan_cap,
+                       long long* scan_len_dev, void* hip_stream);
+
 /* ---- instance metrics between two label maps: contingency table, PQ / AJI / Dice2 / Dice1 counters (cerberus_amd/inst_metrics.py) ------------------
  * Maps are int32 with a row stride in elements (every pixel offset is 64-bit: a view whose last row lies past 2^31 elements is fine); 0 is background
  * and an id outside [1, n_ids] -- negative, or above the bound the caller states -- counts as background too (as in cerb_relabel) and never indexes a

@@ -3,11 +3,12 @@ the MI355X-native InferManager -- HIP forward, on-GPU post-processing, instance 
 pclass_mat/<name>.mat and overlay/<name>.jpg.  Flag names and defaults are the reference's (cerberus_amd/cli.py);
 <model>/settings.yml + weights.tar are read as the reference reads them (run_infer_tile.py:47-49 there); --synthetic
 selects the package's seeded test weights instead (this image has no network to fetch a checkpoint).  `--overlay=device` draws the
-overlay on the device (cerberus_amd/viz.py: overlay_from_parts) instead of with PIL on the writer threads; the default is `host`."""
+overlay on the device (cerberus_amd/viz.py: overlay_from_parts) instead of with PIL on the writer threads; the default is `host`.
+`--overlay_encode=device` (with `--overlay=device`) also JPEG-encodes it there (cerberus_amd/jpeg_encode.py); the default is `host`."""
 import os
 import sys
 
-from cerberus_amd.cli import TILE_OPTIONS, parse, require_model
+from cerberus_amd.cli import TILE_OPTIONS, check_overlay_encode, parse, require_model
 
 
 def main(argv=None):
@@ -15,6 +16,7 @@ def main(argv=None):
     require_model(args)
     if args["--overlay"] not in ("host", "device"):
         sys.exit("--overlay takes host or device, got %r" % args["--overlay"])
+    check_overlay_encode(args, args["--overlay"] == "device", "--overlay=device")
     if args["--gpu"] and "WORLD_SIZE" not in os.environ:
         # `--gpu=0,1`: the reference drives both devices from one process (DataParallel, infer/base.py:46-47); here one rank per listed device,
         # self-spawned (cerberus_amd/launch.py), each taking every w-th file -- or a non-zero exit when the devices are not there
@@ -73,6 +75,7 @@ def main(argv=None):
         "rank": rank,
         "world_size": world,
         "overlay": args["--overlay"],
+        "overlay_encode": args["--overlay_encode"],
     })
     if dist is not None:
         dist.barrier()

@@ -10,7 +10,7 @@ slide also gets `tissue/<slide>.mat` (infer/wsi.py:688-716).  `--auto_mask` make
 1/`--auto_mask_ds` of the processing resolution (the reference's get_tissue_mask, misc/utils.py:195-244); everything after it is the `--msk_dir` path.
 A model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, one canvas channel, PostProcInstErodedMap) is refused by name unless
 `--eroded_maps` is given; with it such heads get one-channel canvases and are labelled through the same bands (not with `--reference_tiling` for nuclei).
-`--save_overlay` also writes `overlay/<slide>.jpg`: the slide at 1/`--overlay_ds` with every instance of the dictionary drawn on it on the device
+`--overlay_encode=device` JPEG-encodes that picture on the device too (cerberus_amd/jpeg_encode.py).  `--save_overlay` also writes `overlay/<slide>.jpg`: the slide at 1/`--overlay_ds` with every instance of the dictionary drawn on it on the device
 (cerberus_amd/viz.py: overlay_from_parts; the reference's visualize_instances_dict, misc/viz_utils.py:150-184).
 
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N run_infer_wsi.py ...`; patch rows shard into one
@@ -24,7 +24,7 @@ import time
 
 import numpy as np
 
-from cerberus_amd.cli import WSI_DRIVER_OPTIONS, parse, require_model
+from cerberus_amd.cli import WSI_DRIVER_OPTIONS, check_overlay_encode, parse, require_model
 
 
 # largest map labelled in one call on one GPU (400 Mpx = 38 GB of workspace); larger slides are labelled in row bands (CERB_ONE_CALL_MPX moves the line)
@@ -162,6 +162,7 @@ def main(argv=None):
     require_model(args)
     _check_auto_mask(args)
     _check_save_overlay(args)
+    check_overlay_encode(args, bool(args["--save_overlay"]), "--save_overlay")
     if args["--jpeg_decode"] not in ("host", "device"):
         sys.exit("--jpeg_decode takes host or device, got %r" % args["--jpeg_decode"])
     if args["--jpeg_decode"] == "device":  # (before the ranks are started: they inherit it)
@@ -560,9 +561,16 @@ def main(argv=None):
             ods = int(args["--overlay_ds"])
             if thumb is None or thumb_ds != ods:
                 thumb = _thumbnail(reader, float(args["--wsi_proc_mag"]), "mpp", ods)
-            picture = overlay_from_parts(thumb, parts, extra=extra, ds=ods, line_width=2).cpu().numpy()
+            picture = overlay_from_parts(thumb, parts, extra=extra, ds=ods, line_width=2)
             os.makedirs(os.path.join(out_dir, "overlay"), exist_ok=True)
-            Image.fromarray(picture).save(os.path.join(out_dir, "overlay", base + ".jpg"))
+            if args["--overlay_encode"] == "device":  # the picture stays where it was drawn: only its compressed bytes come down
+                from cerberus_amd.jpeg_encode import encode_device
+
+                with open(os.path.join(out_dir, "overlay", base + ".jpg"), "wb") as fh:
+                    fh.write(encode_device(picture))
+            else:
+                picture = picture.cpu().numpy()
+                Image.fromarray(picture).save(os.path.join(out_dir, "overlay", base + ".jpg"))
             if log:
                 log.info("Overlay Time: {0} ({1} x {2} picture)".format(time.perf_counter() - t_o, picture.shape[0], picture.shape[1]))
             picture = None
