@@ -15,7 +15,7 @@ EXPORTS = [
     "cerb_target_weight_maps",
     "cerb_valid_stats_bytes", "cerb_valid_stats_reset", "cerb_valid_stats_accumulate",
     "cerb_jpeg_workspace_bytes", "cerb_jpeg_decode_stream", "cerb_jpeg_read_tiles", "cerb_jpeg_decode_window",
-    "cerb_jpeg_enc_workspace_bytes", "cerb_jpeg_enc_coefs", "cerb_jpeg_enc_scan",
+    "cerb_jpeg_enc_workspace_bytes", "cerb_jpeg_enc_coefs", "cerb_jpeg_enc_scan", "cerb_jpeg_enc_tiles_workspace_bytes", "cerb_jpeg_enc_tiles",
     "cerb_tissue_workspace_bytes", "cerb_tissue_hed", "cerb_tissue_entropy", "cerb_tissue_histogram", "cerb_tissue_threshold", "cerb_tissue_morphology",
     "cerb_inst_areas", "cerb_inst_pairs_workspace_bytes", "cerb_inst_pairs", "cerb_inst_pairs_compact", "cerb_inst_pair_stats_workspace_bytes", "cerb_inst_pair_stats",
     "cerb_aug_warp", "cerb_aug_gaussian_blur", "cerb_aug_median_blur", "cerb_aug_gaussian_noise", "cerb_aug_brightness", "cerb_aug_saturation", "cerb_aug_hue",
@@ -198,6 +198,10 @@ def lib():
     L.cerb_jpeg_enc_workspace_bytes.restype = C.c_size_t
     L.cerb_jpeg_enc_coefs.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.cerb_jpeg_enc_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.cerb_jpeg_enc_tiles_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.cerb_jpeg_enc_tiles_workspace_bytes.restype = C.c_size_t
+    L.cerb_jpeg_enc_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
     L.cerb_tissue_workspace_bytes.argtypes = [C.c_int, C.c_int]
     L.cerb_tissue_workspace_bytes.restype = C.c_size_t
     L.cerb_tissue_hed.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

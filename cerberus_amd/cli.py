@@ -76,6 +76,11 @@ WSI_OUTPUT_OPTIONS = [
     ("--overlay_encode", True, "host", "(not in the reference) host | device, with --save_overlay only: where overlay/<slide>.jpg is JPEG-encoded -- host: the picture is "
                                        "downloaded and PIL encodes it; device: it is encoded in HIP (cerb_jpeg_enc_*, cerberus_amd/jpeg_encode.py) and only the "
                                        "compressed bytes are downloaded.  The same pixels on decoding; the file has one restart interval per MCU row"),
+    ("--save_overlay_tiff", False, False, "(not in the reference) write <output_dir>/overlay/<slide>.tif: the slide at the FULL processing resolution with every instance of "
+                                          "dat/<slide>.dat drawn on it (half the tile overlay's line widths), as a pyramidal JPEG-tiled BigTIFF that QuPath, ASAP and "
+                                          "OpenSlide open; drawn, reduced and JPEG-encoded on the device window by window (cerberus_amd/tiff_pyramid.py, "
+                                          "viz.slide_overlay_pyramid).  Independent of --save_overlay, --overlay_ds and --overlay_encode; needs a slide with a reader "
+                                          "(not a `synthetic:` spec)"),
 ]
 
 

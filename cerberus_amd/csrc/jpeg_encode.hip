@@ -10,6 +10,10 @@
 //                         jpeg_enc_offsets_kernel -- exclusive scan of the lengths (+ 2 per RSTm marker), the total to a device word;
 //                         jpeg_enc_pack_kernel   -- per interval: count / scan / expand (FF -> FF 00) straight into its place of the contiguous scan,
 //                                                   the RSTm marker behind it.
+//   cerb_jpeg_enc_tiles : the same coefficients cut into tile x tile crops, each an abbreviated stream of its own (prefix, scan, EOI): the entropy and pack
+//                         kernels take an interval descriptor (Intervals: MCU rows per stream, MCUs per interval, streams across the picture), so an
+//                         interval is one MCU row of ONE TILE -- thousands of workgroups per launch; jpeg_enc_tile_offsets_kernel sums a tile's
+//                         intervals, scans the even-padded tile lengths and writes offsets / counts for the caller.
 // No call allocates or synchronises; everything is queued on the caller's stream.  Equal to PIL / libjpeg-turbo coefficient for coefficient and, with
 // restart_marker_rows = 1, byte for byte in the scan (tests/jpeg_enc_ref.py states the same in numpy).
 #include <hip/hip_runtime.h>
@@ -108,12 +112,31 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // An interval's room BEFORE stuffing.  With the Annex-K tables a block is at most 11 + 11 bits of DC (longest DC code 11, category <= 11) and
 // 63 x (16 + 10) bits of AC (longest AC code 16, category <= 10: 8-bit samples give |AC| <= 1023 at Q = 1): 1660 bits < 208 bytes.  One 32-bit word of
 // slack for the last partial word + the pad, rounded to 128 bytes so that intervals never share a cache line.
-inline size_t slot_bytes(const Geo& g) { return round_up((size_t)g.mc * g.bpm * 208 + 8, 128); }
+inline size_t slot_bytes_of(size_t blocks) { return round_up(blocks * 208 + 8, 128); }
+inline size_t slot_bytes(const Geo& g) { return slot_bytes_of((size_t)g.mc * g.bpm); }
 
 // workspace of cerb_jpeg_enc_scan: [slots: mr x slot_bytes][raw_len: int32 mr][len: int32 mr][off: int64 mr]
 inline size_t scan_ws_bytes(const Geo& g) { return (size_t)g.mr * slot_bytes(g) + round_up((size_t)g.mr * 16, 128); }
 // the finished scan at most: every byte of every interval stuffed + the markers
 inline size_t scan_cap_bytes(const Geo& g) { return (size_t)g.mr * (2 * ((size_t)g.mc * g.bpm * 208 + 1) + 2); }
+
+// How the MCU grid is cut into restart intervals and the intervals into streams.  Interval iv belongs to stream iv / rows (streams row-major over the
+// picture, `across` of them side by side) and is MCU row iv % rows of it: `cols` MCUs.  The whole picture as one stream is {mr, mc, 1}.
+struct Intervals {
+    int rows, cols, across;
+};
+
+// The bytes in front of every tile's scan (SOI SOF0 DRI SOS from the caller), passed BY VALUE.  n = 0 and eoi = 0: the bare scan of cerb_jpeg_enc_scan.
+struct StreamEnds {
+    int n, eoi;
+    uint8_t prefix[64];
+};
+
+// tiles: [slots: n_iv x slot][raw_len: int32 n_iv][len: int32 n_iv][off: int64 n_iv], as scan_ws_bytes
+inline size_t tiles_ws_bytes(size_t n_iv, size_t slot) { return n_iv * slot + round_up(n_iv * 16, 128); }
+// one tile's stream at most: the prefix, every interval stuffed throughout + its marker (RSTm or EOI), the pad byte
+inline size_t tile_cap_bytes(const Intervals& it, int bpm) { return round_up(64 + (size_t)it.rows * (2 * ((size_t)it.cols * bpm * 208 + 1) + 2), 2); }
+
 inline size_t planes_bytes(const Geo& g) { return round_up((size_t)g.yw * g.yh + 2 * (size_t)g.cw * g.ch, 128); }
 
 // ---- planes --------------------------------------------------------------------------------------------------------------------------------------
@@ -310,9 +333,9 @@ __device__ __forceinline__ void jpeg_block_symbols(const int16_t* __restrict__ c
 // byte order of the stream inside a 32-bit word of memory: the word's most significant bit is the earliest bit
 __device__ __forceinline__ unsigned jpeg_be32(unsigned v) { return __builtin_bswap32(v); }
 
-// grid mcu_rows, 256 threads.  Interval `row` = the MCUs of one MCU row; its blocks in coding order are numbered b = m bpm + k (k: the block inside
-// the MCU, Y blocks in raster order, then Cb, then Cr).  The slot must be zero on entry.
-__global__ __launch_bounds__(256) void jpeg_enc_entropy_kernel(const int16_t* __restrict__ coefs, Geo g, HuffTables ht, uint8_t* __restrict__ slots,
+// grid intervals, 256 threads.  Interval iv = it.cols MCUs of MCU row `row`, from MCU column m0 on; its blocks in coding order are numbered
+// b = ml bpm + k (ml: the MCU inside the interval, k: the block inside the MCU, Y blocks in raster order, then Cb, then Cr).  The slot must be zero on entry.
+__global__ __launch_bounds__(256) void jpeg_enc_entropy_kernel(const int16_t* __restrict__ coefs, Geo g, Intervals it, HuffTables ht, uint8_t* __restrict__ slots,
                                                                long long slot_bytes, int* __restrict__ raw_len) {
     __shared__ unsigned part[4];
     __shared__ uint32_t s_dc[2][12];
@@ -322,10 +345,11 @@ __global__ __launch_bounds__(256) void jpeg_enc_entropy_kernel(const int16_t* __
     for (int i = threadIdx.x; i < 512; i += 256) s_ac[i >> 8][i & 255] = ht.ac[i >> 8][i & 255];
     if (threadIdx.x < 64) s_zz[threadIdx.x] = ht.zigzag[threadIdx.x];
     __syncthreads();
-    const int row = blockIdx.x;
-    const int n = g.mc * g.bpm;
+    const int iv = blockIdx.x, strm = iv / it.rows;
+    const int row = (strm / it.across) * it.rows + (iv - strm * it.rows), m0 = (strm % it.across) * it.cols;
+    const int n = it.cols * g.bpm;
     const int ny = g.s * g.s;
-    unsigned* slot = reinterpret_cast<unsigned*>(slots + (long long)row * slot_bytes);
+    unsigned* slot = reinterpret_cast<unsigned*>(slots + (long long)iv * slot_bytes);
     const long long slot_words = slot_bytes >> 2;
     const long long yacross = (long long)g.mc * g.s;
     unsigned long long running = 0;  // bits of the interval laid down so far
@@ -335,22 +359,22 @@ __global__ __launch_bounds__(256) void jpeg_enc_entropy_kernel(const int16_t* __
         const int16_t* c = coefs;
         int pred = 0, tab = 0;
         if (valid) {
-            const int m = b / g.bpm, k = b - m * g.bpm;
+            const int ml = b / g.bpm, k = b - ml * g.bpm, m = m0 + ml;
             if (k < ny) {
-                // Y block k of MCU m, and the Y block coded before it: k - 1 of this MCU, or the last one of MCU m - 1
+                // Y block k of MCU m, and the Y block coded before it: k - 1 of this MCU, or the last one of MCU m - 1 (none at the interval's start)
                 const long long at = ((long long)row * g.s + (k >> (g.s - 1))) * yacross + (long long)m * g.s + (k & (g.s - 1));
                 c = coefs + at * 64;
                 if (k > 0) {
                     const int kp = k - 1;
                     pred = coefs[(((long long)row * g.s + (kp >> (g.s - 1))) * yacross + (long long)m * g.s + (kp & (g.s - 1))) * 64];
-                } else if (m > 0) {
+                } else if (ml > 0) {
                     const int kp = ny - 1;
                     pred = coefs[(((long long)row * g.s + (kp >> (g.s - 1))) * yacross + (long long)(m - 1) * g.s + (kp & (g.s - 1))) * 64];
                 }
             } else {
                 tab = 1;
                 c = coefs + (g.nb0 + (k - ny) * g.nbc + (long long)row * g.mc + m) * 64;
-                if (m > 0) pred = c[-64];
+                if (ml > 0) pred = c[-64];
             }
         }
         unsigned bits = 0;
@@ -382,11 +406,11 @@ __global__ __launch_bounds__(256) void jpeg_enc_entropy_kernel(const int16_t* __
             if (w < slot_words) atomicOr(slot + w, jpeg_be32(v));
         }
         long long bytes = (long long)((running + 7) >> 3);
-        raw_len[row] = (int)(bytes < slot_bytes ? bytes : slot_bytes);
+        raw_len[iv] = (int)(bytes < slot_bytes ? bytes : slot_bytes);
     }
 }
 
-// grid mcu_rows, 256 threads: len[row] = the interval's bytes + its FF bytes
+// grid intervals, 256 threads: len[row] = the interval's bytes + its FF bytes
 __global__ __launch_bounds__(256) void jpeg_enc_count_kernel(const uint8_t* __restrict__ slots, long long slot_bytes, const int* __restrict__ raw_len,
                                                              int* __restrict__ len) {
     __shared__ unsigned part[4];
@@ -420,13 +444,49 @@ __global__ __launch_bounds__(256) void jpeg_enc_offsets_kernel(const int* __rest
     if (threadIdx.x == 0) *scan_len = running;
 }
 
-// grid mcu_rows, 256 threads, 16 source bytes per thread and step: count the FF bytes, scan, write the bytes with a 00 after every FF.  Nothing is
-// written at or past scan_cap.
-__global__ __launch_bounds__(256) void jpeg_enc_pack_kernel(const uint8_t* __restrict__ slots, long long slot_bytes, const int* __restrict__ raw_len,
-                                                            const long long* __restrict__ off, int rows, uint8_t* __restrict__ out, long long scan_cap) {
+// one workgroup, a thread per tile: counts[t] = prefix + the tile's intervals + 2 per interval (RSTm, EOI behind the last); tile_off[t] = exclusive scan
+// of the counts rounded up to even, tile_off[tiles] = the total; off[iv] = where interval iv's bytes start
+__global__ __launch_bounds__(256) void jpeg_enc_tile_offsets_kernel(const int* __restrict__ len, int tiles, int rows, int n_prefix, long long* __restrict__ off,
+                                                                    long long* __restrict__ tile_off, long long* __restrict__ counts) {
     __shared__ unsigned part[4];
-    const int row = blockIdx.x, n = raw_len[row];
+    long long running = 0;
+    for (int base = 0; base < tiles; base += 256) {
+        const int t = base + (int)threadIdx.x;
+        unsigned cnt = 0;
+        if (t < tiles) {
+            cnt = (unsigned)n_prefix;
+            for (int r = 0; r < rows; ++r) cnt += (unsigned)len[(long long)t * rows + r] + 2u;
+        }
+        unsigned total;
+        const unsigned ex = block_scan_256((cnt + 1u) & ~1u, part, &total);  // (256 tiles of <= 64 intervals of < 2^17 bytes: the chunk's sum fits 32 bits)
+        if (t < tiles) {
+            long long at = running + ex;
+            tile_off[t] = at;
+            counts[t] = cnt;
+            at += n_prefix;
+            for (int r = 0; r < rows; ++r) {
+                off[(long long)t * rows + r] = at;
+                at += len[(long long)t * rows + r] + 2;
+            }
+        }
+        running += total;
+    }
+    if (threadIdx.x == 0) tile_off[tiles] = running;
+}
+
+// grid intervals, 256 threads, 16 source bytes per thread and step: count the FF bytes, scan, write the bytes with a 00 after every FF.  Interval `row`
+// is interval row % rows of its stream: the first one puts the stream's prefix in front, every one but the last RSTm behind, the last one EOI and the
+// zero byte that makes the stream's length even (ends.eoi; a stream starts at an even offset).  Nothing is written at or past scan_cap.
+__global__ __launch_bounds__(256) void jpeg_enc_pack_kernel(const uint8_t* __restrict__ slots, long long slot_bytes, const int* __restrict__ raw_len,
+                                                            const long long* __restrict__ off, int rows, StreamEnds ends, uint8_t* __restrict__ out,
+                                                            long long scan_cap) {
+    __shared__ unsigned part[4];
+    const int row = blockIdx.x, n = raw_len[row], r = row % rows;
     const uint4* src = reinterpret_cast<const uint4*>(slots + (long long)row * slot_bytes);
+    if (r == 0 && (int)threadIdx.x < ends.n) {
+        const long long o = off[row] - ends.n + threadIdx.x;
+        if (o < scan_cap) out[o] = ends.prefix[threadIdx.x];
+    }
     long long at = off[row];
     for (int base = 0; base < n; base += 256 * 16) {
         const int p0 = base + (int)threadIdx.x * 16;
@@ -455,9 +515,10 @@ __global__ __launch_bounds__(256) void jpeg_enc_pack_kernel(const uint8_t* __res
         const int took = n - base < 256 * 16 ? n - base : 256 * 16;
         at += took + total;
     }
-    if (threadIdx.x == 0 && row < rows - 1) {
+    if (threadIdx.x == 0 && (r < rows - 1 || ends.eoi)) {
         if (at < scan_cap) out[at] = 0xFF;
-        if (at + 1 < scan_cap) out[at + 1] = (uint8_t)(0xD0 + (row & 7));
+        if (at + 1 < scan_cap) out[at + 1] = r < rows - 1 ? (uint8_t)(0xD0 + (r & 7)) : (uint8_t)0xD9;
+        if (r == rows - 1 && (at & 1) && at + 2 < scan_cap) out[at + 2] = 0;
     }
 }
 
@@ -533,13 +594,87 @@ extern "C" int cerb_jpeg_enc_scan(const int16_t* coefs, int w, int h, int subsam
     long long* off = (long long*)(len + g.mr);
     const hipError_t e = hipMemsetAsync(slots, 0, (size_t)g.mr * slot, st);
     if (e != hipSuccess) return cerb_set_error(std::string(fn) + ": " + hipGetErrorString(e));
-    hipLaunchKernelGGL(jpeg_enc_entropy_kernel, dim3(g.mr), dim3(256), 0, st, coefs, g, ht, slots, (long long)slot, raw_len);
+    const Intervals whole{g.mr, g.mc, 1};
+    const StreamEnds bare{};
+    hipLaunchKernelGGL(jpeg_enc_entropy_kernel, dim3(g.mr), dim3(256), 0, st, coefs, g, whole, ht, slots, (long long)slot, raw_len);
     if (launched(fn)) return 1;
     hipLaunchKernelGGL(jpeg_enc_count_kernel, dim3(g.mr), dim3(256), 0, st, (const uint8_t*)slots, (long long)slot, (const int*)raw_len, len);
     if (launched(fn)) return 1;
     hipLaunchKernelGGL(jpeg_enc_offsets_kernel, dim3(1), dim3(256), 0, st, (const int*)len, g.mr, off, scan_len_dev);
     if (launched(fn)) return 1;
     hipLaunchKernelGGL(jpeg_enc_pack_kernel, dim3(g.mr), dim3(256), 0, st, (const uint8_t*)slots, (long long)slot, (const int*)raw_len, (const long long*)off, g.mr,
-                       scan_out, (long long)scan_cap);
+                       bare, scan_out, (long long)scan_cap);
+    return launched(fn);
+}
+
+namespace {
+
+// the tile grid of cerb_jpeg_enc_tiles, or false with `why` naming the argument
+bool tile_grid(int w, int h, int tile, int subsampling, Geo* g, Intervals* it, std::string* why) {
+    if (w < 1 || h < 1 || w > 32768 || h > 32768) *why = "the picture's width and height must lie in 1 .. 32768, got " + std::to_string(w) + " x " + std::to_string(h);
+    else if (subsampling != 0 && subsampling != 2) *why = "subsampling must be 0 (4:4:4) or 2 (4:2:0), got " + std::to_string(subsampling);
+    else if (tile < 16 || tile > 512 || tile % 16) *why = "tile must be a multiple of 16 in 16 .. 512, got " + std::to_string(tile);
+    else if (w % tile || h % tile) *why = "w and h must be multiples of tile " + std::to_string(tile) + ", got " + std::to_string(w) + " x " + std::to_string(h);
+    else {
+        *g = make_geo(w, h, subsampling);
+        *it = Intervals{tile / (8 * g->s), tile / (8 * g->s), w / tile};
+        return true;
+    }
+    return false;
+}
+
+}  // namespace
+
+extern "C" size_t cerb_jpeg_enc_tiles_workspace_bytes(int w, int h, int tile, int subsampling, int which) {
+    Geo g;
+    Intervals it;
+    std::string why;
+    if (!tile_grid(w, h, tile, subsampling, &g, &it, &why)) return 0;
+    const size_t tiles = (size_t)(w / tile) * (h / tile);
+    switch (which) {
+        case 0: return tiles_ws_bytes(tiles * it.rows, slot_bytes_of((size_t)it.cols * g.bpm));
+        case 1: return tiles * tile_cap_bytes(it, g.bpm);
+        default: return 0;
+    }
+}
+
+extern "C" int cerb_jpeg_enc_tiles(const int16_t* coefs, int w, int h, int tile, int subsampling, const uint8_t* prefix, int n_prefix, void* workspace,
+                                   size_t ws_bytes, uint8_t* out, size_t out_cap, long long* offsets_dev, long long* counts_dev, void* hip_stream) {
+    const char* fn = "cerb_jpeg_enc_tiles";
+    Geo g;
+    Intervals it;
+    std::string why;
+    if (!tile_grid(w, h, tile, subsampling, &g, &it, &why)) return cerb_set_error(std::string(fn) + ": " + why);
+    if (n_prefix < 0 || n_prefix > 64) return cerb_set_error(std::string(fn) + ": n_prefix must lie in 0 .. 64, got " + std::to_string(n_prefix));
+    if (!coefs || !workspace || !out || !offsets_dev || !counts_dev || (n_prefix && !prefix))
+        return cerb_set_error(std::string(fn) + ": a null pointer (coefs, prefix, workspace, out, offsets_dev or counts_dev)");
+    if (((uintptr_t)coefs & 15) || ((uintptr_t)workspace & 127) || ((uintptr_t)offsets_dev & 7) || ((uintptr_t)counts_dev & 7))
+        return cerb_set_error(std::string(fn) + ": misaligned: coefs needs 16 bytes, workspace 128, offsets_dev and counts_dev 8");
+    const int tiles = (w / tile) * (h / tile);
+    const long long n_iv = (long long)tiles * it.rows;
+    const size_t slot = slot_bytes_of((size_t)it.cols * g.bpm);
+    if (ws_bytes < tiles_ws_bytes((size_t)n_iv, slot))
+        return cerb_set_error(std::string(fn) + ": the workspace is too small: " + std::to_string(ws_bytes) + " bytes, cerb_jpeg_enc_tiles_workspace_bytes(.., 0) = " +
+                              std::to_string(tiles_ws_bytes((size_t)n_iv, slot)));
+    static const HuffTables ht = make_huff_tables();
+    StreamEnds ends{};
+    ends.n = n_prefix;
+    ends.eoi = 1;
+    for (int i = 0; i < n_prefix; ++i) ends.prefix[i] = prefix[i];
+    hipStream_t st = (hipStream_t)hip_stream;
+    uint8_t* slots = (uint8_t*)workspace;
+    int* raw_len = (int*)(slots + (size_t)n_iv * slot);
+    int* len = raw_len + n_iv;
+    long long* off = (long long*)(len + n_iv);
+    const hipError_t e = hipMemsetAsync(slots, 0, (size_t)n_iv * slot, st);
+    if (e != hipSuccess) return cerb_set_error(std::string(fn) + ": " + hipGetErrorString(e));
+    hipLaunchKernelGGL(jpeg_enc_entropy_kernel, dim3((unsigned)n_iv), dim3(256), 0, st, coefs, g, it, ht, slots, (long long)slot, raw_len);
+    if (launched(fn)) return 1;
+    hipLaunchKernelGGL(jpeg_enc_count_kernel, dim3((unsigned)n_iv), dim3(256), 0, st, (const uint8_t*)slots, (long long)slot, (const int*)raw_len, len);
+    if (launched(fn)) return 1;
+    hipLaunchKernelGGL(jpeg_enc_tile_offsets_kernel, dim3(1), dim3(256), 0, st, (const int*)len, tiles, it.rows, n_prefix, off, offsets_dev, counts_dev);
+    if (launched(fn)) return 1;
+    hipLaunchKernelGGL(jpeg_enc_pack_kernel, dim3((unsigned)n_iv), dim3(256), 0, st, (const uint8_t*)slots, (long long)slot, (const int*)raw_len, (const long long*)off,
+                       it.rows, ends, out, (long long)out_cap);
     return launched(fn);
 }

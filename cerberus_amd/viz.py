@@ -225,6 +225,159 @@ def overlay_from_parts(image, parts, extra=None, viz_info=None, up=1, ds=1, orig
     return draw_contours_device(image, pack_parts(parts, extra, viz_info, ds, origin, line_width), up)
 
 
+def half_width_viz_info(viz_info=None):
+    """viz_info with every line width halved, at least 1 (gland 6, lumen 6, nuclei 1): the tile overlay draws the full widths on a picture at x2
+    magnification, so this is the same look on one at x1."""
+    viz_info = DEFAULT_VIZ_INFO if viz_info is None else viz_info
+    return {k: dict(v, line_width=max(1, int(v["line_width"]) // 2)) for k, v in viz_info.items()}
+
+
+def _pad_edge_(pic, hv, wv):
+    """edge replication, in place, of the valid hv x wv pixels of a device picture out to its full size (np.pad(valid, mode="edge"))"""
+    if wv < pic.shape[1]:
+        pic[:hv, wv:] = pic[:hv, wv - 1:wv]
+    if hv < pic.shape[0]:
+        pic[hv:] = pic[hv - 1:hv]
+
+
+def pyramid_windows(width, height, tile, rows):
+    """[(x0, y0, x1, y1)] of level 0: row strips `rows` high, cut into column windows where the slide is wider than 32768; sides are multiples of
+    2 tile (so every window starts at an even pixel and on the tile grid) except where the slide ends"""
+    cols = OVERLAY_MAX_SIDE // (2 * tile) * (2 * tile)
+    return [(x0, y0, min(x0 + cols, width), min(y0 + rows, height)) for y0 in range(0, height, rows) for x0 in range(0, width, cols)]
+
+
+def pyramid_device_bytes(width, height, tile, rows):
+    """what slide_overlay_pyramid holds on the device for a window height of `rows`: (resident levels 1 .., one window: pixels read + picture drawn +
+    padded picture, the overlay plane, the tile encoder)"""
+    from .tiff_pyramid import TileEncoder, level_sizes
+
+    def up(v):
+        return -(-v // tile) * tile
+
+    sizes = level_sizes(width, height, tile)
+    cw, ch = min(up(width), OVERLAY_MAX_SIDE // (2 * tile) * (2 * tile)), min(up(height), rows)
+    resident = sum(3 * up(w) * up(h) for w, h in sizes[1:])
+    return resident, 9 * cw * ch, 4 * cw * ch, TileEncoder.price(cw, ch, tile)
+
+
+def slide_overlay_pyramid(reader, proc_res, parts, extra, path, tile=256, quality=75, viz_info=None, window_rows=None, timings=None):
+    """The slide at the processing resolution (proc_res microns per pixel, as tissue.thumbnail reads it at ds = 1) with every instance of `parts` and
+    `extra` (see pack_parts) drawn on it at HALF the tissue's line width, written to `path` as a pyramidal JPEG-tiled BigTIFF
+    (cerberus_amd/tiff_pyramid.py; 4:2:0).  Level 0 is walked in windows (pyramid_windows): pixels from reader.read_bounds, strokes from
+    draw_contours_device through a translated origin, each window reduced x2 (cerb_resample_box: exact means, half to even, clamped at the slide's
+    edge) into a RESIDENT level 1 and encoded tile by tile on the device; levels 1, 2, .. are then encoded in windows and reduced in turn.  Padding
+    out to the tile grid replicates the edge of the level's own pixels.  Memory is priced before anything is allocated: window_rows=None takes the
+    tallest window that fits (a multiple of 2 tile), and a slide that does not fit with the smallest raises ValueError naming the bytes.
+    timings: a dictionary that receives seconds per stage (read, draw, reduce, encode, download, write; the device is then waited for between the
+    stages), the file's size and the peak device bytes.  -> [(w, h)] of the levels."""
+    import ctypes as C
+    import os
+    import time
+
+    import torch
+
+    from . import _lib
+    from .tiff_pyramid import PyramidWriter, TileEncoder, check_tile, level_sizes
+
+    tile = check_tile(tile)
+    s = reader._scale(proc_res, "mpp")
+    W, H = (max(1, int(v)) for v in reader.slide_dimensions(s, "baseline"))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    step = 2 * tile
+
+    def up(v, m=tile):
+        return -(-v // m) * m
+
+    free = int(torch.cuda.mem_get_info(dev)[0])
+    if window_rows is None:
+        # at most 2^26 pixels a window (more brings no more parallelism), halved until the device has room
+        rows = max(step, min(up(H, step), OVERLAY_MAX_SIDE // step * step, (1 << 26) // min(up(W), OVERLAY_MAX_SIDE) // step * step))
+        while rows > step and sum(pyramid_device_bytes(W, H, tile, rows)) > 0.9 * free:
+            rows = max(step, rows // 2 // step * step)
+    else:
+        rows = int(window_rows)
+        if rows < step or rows % step or rows > OVERLAY_MAX_SIDE:
+            raise ValueError("slide_overlay_pyramid: window_rows must be a multiple of 2 tile = %d up to %d, got %r" % (step, OVERLAY_MAX_SIDE, window_rows))
+    need = pyramid_device_bytes(W, H, tile, rows)
+    if sum(need) > 0.9 * free:
+        raise ValueError("slide_overlay_pyramid: a %d x %d slide at tile %d needs %d bytes on the device with the smallest window (%d rows): %d for the resident "
+                         "levels, %d for a window, %d for the overlay plane, %d for the tile encoder; %d are free"
+                         % ((W, H, tile, sum(need), rows) + need + (free,)))
+    L = _lib.lib()
+    sizes = level_sizes(W, H, tile)
+    proc_mpp = float(np.atleast_1d(proc_res)[0]) if reader.info.mpp is not None else None
+    writer = PyramidWriter(path, W, H, tile, quality, 2, mpp=proc_mpp)
+    took = dict.fromkeys(("read", "draw", "reduce", "encode", "download", "write"), 0.0)
+    clock = [time.perf_counter()]
+
+    def lap(stage):
+        if timings is not None:
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            took[stage] += now - clock[0]
+            clock[0] = now
+
+    def emit(enc, level, pic, x0, y0):
+        """the tiles of `pic`, whose top left tile is the level's tile (y0 / tile, x0 / tile), encoded and appended to the file"""
+        handle = enc.encode(pic, quality, 2)
+        lap("encode")
+        data, offsets, counts = handle.tiles()
+        lap("download")
+        across = writer.grids[level][0]
+        ty, tx = np.mgrid[0:pic.shape[0] // tile, 0:pic.shape[1] // tile]
+        writer.add_tiles(level, ((ty + y0 // tile) * across + tx + x0 // tile).reshape(-1), data, offsets, counts)
+        lap("write")
+
+    def reduce(src, hv, wv, dst):
+        """dst (a view whose first pixel is the one src's first 2 x 2 box becomes) <- the x2 reduction of src's valid hv x wv pixels"""
+        _lib.check(L.cerb_resample_box(src.data_ptr(), int(src.stride(0)), hv, wv, 2, dst.data_ptr(), int(dst.stride(0)), -(-hv // 2), -(-wv // 2),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    try:
+        if timings is not None:
+            torch.cuda.reset_peak_memory_stats(dev)
+        with torch.cuda.device(dev):
+            levels = [None] + [torch.empty((up(h), up(w), 3), dtype=torch.uint8, device=dev) for w, h in sizes[1:]]
+            cw = min(up(W), OVERLAY_MAX_SIDE // step * step)
+            enc = TileEncoder(dev, cw, min(up(H), rows), tile)
+            pic = torch.empty((min(up(H), rows), cw, 3), dtype=torch.uint8, device=dev)
+            groups = pack_parts(parts, extra, half_width_viz_info(viz_info), ds=1, origin=(0, 0))
+            for g in groups:  # uploaded once; a window only moves the origin
+                g["points"], g["offsets"], g["counts"], g["colours"] = _group_to_device(g, dev)
+            clock[0] = time.perf_counter()
+            for x0, y0, x1, y1 in pyramid_windows(W, H, tile, rows):
+                hv, wv = y1 - y0, x1 - x0
+                pixels = torch.from_numpy(np.ascontiguousarray(reader.read_bounds((x0, y0, x1, y1), resolution=s, units="baseline")[..., :3])).to(dev)
+                lap("read")
+                drawn = draw_contours_device(pixels, [dict(g, origin=(x0, y0)) for g in groups])
+                lap("draw")
+                if len(sizes) > 1:
+                    reduce(drawn, hv, wv, levels[1][y0 // 2:, x0 // 2:])
+                    lap("reduce")
+                view = pic[:up(hv), :up(wv)]
+                view[:hv, :wv] = drawn
+                _pad_edge_(view, hv, wv)
+                emit(enc, 0, view, x0, y0)
+                pixels = drawn = None
+            for k in range(1, len(sizes)):
+                w, h = sizes[k]
+                if k + 1 < len(sizes):
+                    reduce(levels[k], h, w, levels[k + 1])
+                _pad_edge_(levels[k], h, w)
+                lap("reduce")
+                for x0, y0, x1, y1 in pyramid_windows(up(w), up(h), tile, min(up(H), rows)):
+                    emit(enc, k, levels[k][y0:y1, x0:x1], x0, y0)
+                levels[k] = None
+        writer.close()
+    except BaseException:
+        writer.abort()
+        raise
+    if timings is not None:
+        timings.update(took, file_bytes=os.path.getsize(path), peak_device_bytes=int(torch.cuda.max_memory_allocated(dev)), window_rows=rows)
+    return sizes
+
+
 def visualize_instances_dict_device(input_image, inst_dict_, viz_info=None):
     """visualize_instances_dict_orig for callers who hold a dictionary, drawn on the device: same arguments, same kind of result (a new uint8 RGB
     numpy array), same tissue order, colours and widths; the stroke is the integer definition of include/cerberus_hip.h instead of PIL's."""

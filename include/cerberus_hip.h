@@ -539,7 +539,21 @@ int cerb_jpeg_decode_window(const void* dev_buf, size_t dev_bytes, int n_tiles, 
  *                           between the intervals, none after the last.  workspace: 128-byte aligned.  *scan_len_dev (int64 on the device) is the
  *                           scan's full length; bytes at or past scan_cap are not written, so a caller that gave less than
  *                           cerb_jpeg_enc_workspace_bytes(.., 3) compares the two.  One memset and four launches.
- * Both refuse BEFORE any launch (1, cerb_last_error names the argument): w or h outside 1 .. 32768, quality outside 1 .. 100, subsampling other than
+ *   cerb_jpeg_enc_tiles     the coefficients of a w x h picture -> one abbreviated stream per tile x tile crop (the tiles of a JPEG-in-TIFF page;
+ *                           cerberus_amd/tiff_pyramid.py).  w and h are multiples of tile, tile a multiple of 16 in 16 .. 512: the MCU grid, the 2 x 2
+ *                           chroma boxes and the blocks then align with the tile grid, the crop's coefficients are a sub-raster of the picture's and
+ *                           nothing is recomputed.  Tile i (row-major) becomes prefix[0 .. n_prefix) + the scan of the crop EXACTLY as
+ *                           cerb_jpeg_enc_scan defines it for a tile x tile picture (an interval per MCU row of the tile, RSTm with m = the row
+ *                           inside the tile mod 8, none after the last) + FF D9.  prefix: HOST bytes, n_prefix <= 64, copied into the launch
+ *                           arguments (the caller's SOI SOF0 DRI SOS: 41 bytes).  offsets_dev: int64 [n_tiles + 1] on the device, offsets_dev[i]
+ *                           the start of tile i in out -- always even, a zero byte follows a stream of odd length -- and offsets_dev[n_tiles] the
+ *                           total; counts_dev: int64 [n_tiles], the unpadded lengths.  Bytes at or past out_cap are not written and the total is
+ *                           reported all the same.  cerb_jpeg_enc_tiles_workspace_bytes(w, h, tile, subsampling, which): 0 the workspace (128-byte
+ *                           aligned), 1 the out_cap that never truncates; 0 for arguments the call refuses.  Integer atomics only: the bytes do not
+ *                           depend on the order of execution.  One memset and four launches; an interval has at most 192 blocks (one pass of a
+ *                           workgroup).  Refuses before any launch, naming the argument: a bad tile, w or h no multiple of it, a workspace too small
+ *                           or misaligned, a null pointer, n_prefix outside 0 .. 64.
+ * All refuse BEFORE any launch (1, cerb_last_error names the argument): w or h outside 1 .. 32768, quality outside 1 .. 100, subsampling other than
  * 0 (4:4:4) / 2 (4:2:0), a workspace smaller than cerb_jpeg_enc_workspace_bytes says.  They queue on hip_stream, allocate nothing, do not synchronise.
  * Capacity: with the Annex-K tables a block takes at most 11 + 11 bits of DC and 63 x (16 + 10) bits of AC = 1660 bits < 208 bytes, so an interval of n
  * blocks has a slot of 208 n bytes (+ 8, rounded to 128) before stuffing and at most twice that + 2 in the scan: no 8-bit picture overruns at any
@@ -564,6 +578,9 @@ int cerb_jpeg_enc_coefs(const uint8_t* src, long long row_stride, int w, int h, 
                         void* workspace, size_t ws_bytes, void* hip_stream);
 int cerb_jpeg_enc_scan(const int16_t* coefs, int w, int h, int subsampling, void* workspace, size_t ws_bytes, uint8_t* scan_out, size_t scan_cap,
                        long long* scan_len_dev, void* hip_stream);
+size_t cerb_jpeg_enc_tiles_workspace_bytes(int w, int h, int tile, int subsampling, int which);
+int cerb_jpeg_enc_tiles(const int16_t* coefs, int w, int h, int tile, int subsampling, const uint8_t* prefix, int n_prefix, void* workspace,
+                        size_t ws_bytes, uint8_t* out, size_t out_cap, long long* offsets_dev, long long* counts_dev, void* hip_stream);
 
 /* ---- instance metrics between two label maps: contingency table, PQ / AJI / Dice2 / Dice1 counters (cerberus_amd/inst_metrics.py) ------------------
  * Maps are int32 with a row stride in elements (every pixel offset is 64-bit: a view whose last row lies past 2^31 elements is fine); 0 is background

@@ -12,6 +12,8 @@ A model whose INST heads carry the IP-ERODED-3 / -11 codes (two classes, one can
 `--eroded_maps` is given; with it such heads get one-channel canvases and are labelled through the same bands (not with `--reference_tiling` for nuclei).
 `--overlay_encode=device` JPEG-encodes that picture on the device too (cerberus_amd/jpeg_encode.py).  `--save_overlay` also writes `overlay/<slide>.jpg`: the slide at 1/`--overlay_ds` with every instance of the dictionary drawn on it on the device
 (cerberus_amd/viz.py: overlay_from_parts; the reference's visualize_instances_dict, misc/viz_utils.py:150-184).
+`--save_overlay_tiff` writes `overlay/<slide>.tif`: the same instances on the slide at the FULL processing resolution as a pyramidal JPEG-tiled BigTIFF
+for slide viewers, drawn, reduced and encoded on the device window by window (cerberus_amd/viz.py: slide_overlay_pyramid; cerberus_amd/tiff_pyramid.py).
 
 Multi-GPU: launch under `python -m torch.distributed.run --nproc-per-node N run_infer_wsi.py ...`; patch rows shard into one
 contiguous band per rank, inference needs no collective, post-processing is band-local (cerberus_amd/shard_postproc.py)."""
@@ -157,11 +159,21 @@ def _check_save_overlay(args):
                 fh.close()
 
 
+def _check_save_overlay_tiff(args):
+    """--save_overlay_tiff is refused, before a device is touched, for a `synthetic:<H>x<W>:<seed>` spec: it has no reader to take the pixels from."""
+    if not args["--save_overlay_tiff"]:
+        return
+    for p in _slide_list(args):
+        if os.path.splitext(p)[1].lower() == ".txt":
+            raise ValueError("--save_overlay_tiff: %s is a synthetic slide spec (`synthetic:<H>x<W>:<seed>`): it has no reader to take the picture from" % os.path.basename(p))
+
+
 def main(argv=None):
     args = parse("run_infer_wsi.py", WSI_DRIVER_OPTIONS, argv, version="CoBi Gland Inference")
     require_model(args)
     _check_auto_mask(args)
     _check_save_overlay(args)
+    _check_save_overlay_tiff(args)
     check_overlay_encode(args, bool(args["--save_overlay"]), "--save_overlay")
     if args["--jpeg_decode"] not in ("host", "device"):
         sys.exit("--jpeg_decode takes host or device, got %r" % args["--jpeg_decode"])
@@ -574,6 +586,14 @@ def main(argv=None):
             if log:
                 log.info("Overlay Time: {0} ({1} x {2} picture)".format(time.perf_counter() - t_o, picture.shape[0], picture.shape[1]))
             picture = None
+        if args["--save_overlay_tiff"]:  # the same instances on the slide at the full processing resolution, as a pyramidal JPEG-tiled BigTIFF
+            from cerberus_amd.viz import slide_overlay_pyramid
+
+            t_o = time.perf_counter()
+            os.makedirs(os.path.join(out_dir, "overlay"), exist_ok=True)
+            tiff_levels = slide_overlay_pyramid(reader, float(args["--wsi_proc_mag"]), parts, extra, os.path.join(out_dir, "overlay", base + ".tif"))
+            if log:
+                log.info("Overlay TIFF Time: {0} ({1} levels, level 0 {2} x {3})".format(time.perf_counter() - t_o, len(tiff_levels), tiff_levels[0][1], tiff_levels[0][0]))
         thumb = None
         t4 = time.perf_counter()
         print("%s: Inference Time: %.3f  Post Proc Time: %.3f  Instance Table Time: %.3f  (%.1f Mpx/s inference)" % (
