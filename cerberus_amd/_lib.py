@@ -18,6 +18,7 @@ EXPORTS = [
     "cerb_jpeg_enc_workspace_bytes", "cerb_jpeg_enc_coefs", "cerb_jpeg_enc_scan", "cerb_jpeg_enc_tiles_workspace_bytes", "cerb_jpeg_enc_tiles",
     "cerb_tissue_workspace_bytes", "cerb_tissue_hed", "cerb_tissue_entropy", "cerb_tissue_histogram", "cerb_tissue_threshold", "cerb_tissue_morphology",
     "cerb_inst_areas", "cerb_inst_pairs_workspace_bytes", "cerb_inst_pairs", "cerb_inst_pairs_compact", "cerb_inst_pair_stats_workspace_bytes", "cerb_inst_pair_stats",
+    "cerb_inst_shape", "cerb_inst_hull_rows", "cerb_inst_relate", "cerb_points_knn",
     "cerb_aug_warp", "cerb_aug_gaussian_blur", "cerb_aug_median_blur", "cerb_aug_gaussian_noise", "cerb_aug_brightness", "cerb_aug_saturation", "cerb_aug_hue",
     "cerb_aug_contrast", "cerb_aug_channel_sums",
     "cerb_overlay_workspace_bytes", "cerb_overlay_clear", "cerb_overlay_stamp", "cerb_overlay_resolve",
@@ -219,7 +220,13 @@ def lib():
     L.cerb_inst_pair_stats_workspace_bytes.restype = C.c_size_t
     L.cerb_inst_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.cerb_aug_warp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_inst_shape.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cerb_inst_hull_rows.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]
+    L.cerb_inst_relate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
+    L.cerb_points_knn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cerb_aug_warp.argtypes =[C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.cerb_aug_gaussian_blur.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cerb_aug_median_blur.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.cerb_aug_gaussian_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -102,6 +102,16 @@ STATS_OPTIONS = [
     ("--types", True, None, "number of classes, background included: also report PQ per class 1 .. n-1 and their mean (needs 'inst_type' on the true side)"),
 ]
 
+# compute_features.py (not in the reference: its misc/viz_utils.py visualize_graph sketches the gland graph these tables feed)
+FEATURES_OPTIONS = [
+    ("--gpu", True, "0", "GPU id, exported as HIP_VISIBLE_DEVICES"),
+    ("--pred_dir", True, None, "the --output_dir of run_infer_tile.py: <pred_dir>/{nuclei,gland,lumen}_mat/<name>.mat are read ('inst_map', 'id', 'type'); "
+                               "<pred_dir>/features/<name>_{nuclei,gland,lumen}.csv are written"),
+    ("--npz", True, None, "a <slide>.npz of run_infer_wsi.py --save_label_maps (keys Nuclei, Gland, Lumen, type_*): gland and lumen maps at the nuclei "
+                          "map's resolution or at half of it; the CSVs are written to <directory of the file>/features/"),
+    ("--knn", True, "4", "neighbours per gland in the gland table (1 .. 8; 0: none)"),
+]
+
 
 def usage(prog, options):
     lines = ["usage: %s [options]" % prog, "", "options:", "  -h, --help", "  --version"]

@@ -621,6 +621,58 @@ int cerb_inst_pair_stats(const long long* keys, const long long* counts, long lo
                          const long long* pred_area, int n_pred, const int32_t* true_type, const int32_t* pred_type, int cls,
                          long long* summary, double* sum_iou, void* ws, size_t ws_bytes, void* hip_stream);
 
+/* ---- instance morphometry and relations between tissues (cerberus_amd/inst_features.py, csrc/inst_features.hip) ---------------------------------------
+ * House rules of cerb_inst_*: maps are int32 with a row stride in elements and 64-bit pixel offsets; id 0 is background and so is any id outside
+ * [1, n_inst] (negative or above the bound), which never indexes a table; nothing outside h x w is read; every call queues on hip_stream, allocates
+ * nothing and does not synchronise.  `table` is cerb_inst_table's output for the SAME map and n_inst (int64 [n_inst][16]).
+ *
+ * cerb_inst_shape  shape: device int64 [n_inst][CERB_INST_SHAPE_WORDS], CLEARED by this call (all eight words), row id-1 =
+ *       {m20, m02, m11, crack, border_px, hull_area2, hull_pts, rows}.  This call fills words 0..4; cerb_inst_hull_rows, called AFTER it, words 5..7.
+ *     m20 = sum (x - x1)^2, m02 = sum (y - y1)^2, m11 = sum (x - x1)(y - y1) over the instance's pixels, (y1, x1) = the box corner table[.][3], [5]:
+ *       raw second moments about the box corner.  Exact in int64 while every box side is < 2^16 and every area < 2^31 (each term < 2^32).
+ *     crack = number of (pixel of the instance, one of its four neighbour directions) pairs whose neighbour lies outside the map or carries another
+ *       id (background and out-of-range ids included; the neighbour is validated like the centre pixel): the 4-connected boundary length in pixel
+ *       edges.  An edge between two touching instances counts for both.
+ *     border_px = number of the instance's pixels with at least one such side.
+ *     One lane per run of equal labels along a row inside a wave issues the atomics (3 for a run without a boundary side, 5 otherwise).
+ *
+ * cerb_inst_hull_rows  the convex hull of the instance's pixel CENTRES, in two passes behind one call.
+ *     row_offsets: int64 [n_inst], the exclusive scan of the box heights max(y2 - y1, 0) (0 for an absent id).  extents: int32 [sum of box heights][2],
+ *       cleared by the call to the empty sentinel {INT_MAX, INT_MIN}; pass 1 leaves {leftmost x, rightmost x} of the instance in every row of its box
+ *       (a row without a pixel of the instance -- an instance of several pieces -- keeps the sentinel).  Pass 2 uses `extents` as its stacks: on
+ *       return its content is unspecified.
+ *     Pass 2, one thread per instance: the hull of a pixel set is the hull of its per-row extremes; a monotone chain over the left ends and one over
+ *       the right ends, rows top to bottom, empty rows skipped, collinear points dropped (vertices are strict).
+ *       shape[.][5] = hull_area2: twice the polygon's area (shoelace sum, an exact integer; 0 for a point or a line);
+ *       shape[.][6] = hull_pts: number of strict vertices -- 1 for a single pixel, 2 for any straight line of pixels;
+ *       shape[.][7] = rows: rows of the box with at least one pixel.  All three are 0 for an absent id and -1 for a box side >= 2^16 (not computed).
+ *     hull_pts_out: int32 [2 x sum of box heights][2] or NULL (areas only).  The vertices of instance i start at point slot 2 * row_offsets[i], x then
+ *       y, at most 2 x box height of them, counter-clockwise on the screen (y down) from the top-left vertex (the leftmost pixel of the top row): down
+ *       the left side, along the bottom, up the right side.  Slots past hull_pts are not written.
+ *
+ * cerb_inst_relate  one thread per child instance i (row i of child_table, a cerb_inst_table of the CHILD map): its integer centroid is
+ *       (cx, cy) = (sum_x / area, sum_y / area), floor division; parent_of[i] = parent_labels[cy >> shift][cx >> shift], and 0 when that pixel lies
+ *       outside ph x pw, holds an id outside [1, n_parent], or the child is absent (area 0).  parent_of: int32 [n_child].
+ *     parent_rows: int64 [n_parent][CERB_INST_PARENT_WORDS], cleared by the call; the row of parent p (row p-1) gains {children, sum of child areas,
+ *       children of class 0..7} with class = child_type[i] & 7 (child_type: int32 [n_child] or NULL = the class columns stay 0).
+ *     shift is 0 when both maps share a grid and 1 when the child map is at full resolution and the parent map at x0.5.  Child areas are in CHILD-map
+ *       pixels whatever the shift.
+ *
+ * cerb_points_knn  xy: int32 [n][2], coordinates of absolute value < 2^26; 1 <= k <= 8.  idx_out: int32 [n][k], the k nearest OTHER points by exact
+ *       int64 squared distance, ascending by (d2, index) -- a tie goes to the smaller index; -1 fills the row where n - 1 < k.  d2_out: int64 [n][k],
+ *       -1 beside a -1 index.  Brute force, n^2 distances (candidate tiles staged through LDS, k best per thread in registers): meant for gland and
+ *       lumen graphs of 10^3..10^5 points. */
+#define CERB_INST_SHAPE_WORDS 8
+#define CERB_INST_PARENT_WORDS 10
+int cerb_inst_shape(const int32_t* labels, long long lab_row_stride, int h, int w, int n_inst, const long long* table, long long* shape,
+                    void* hip_stream);
+int cerb_inst_hull_rows(const int32_t* labels, long long lab_row_stride, int h, int w, int n_inst, const long long* table,
+                        const long long* row_offsets, int32_t* extents, int32_t* hull_pts_out, long long* shape, void* hip_stream);
+int cerb_inst_relate(const long long* child_table, int n_child, const int32_t* child_type, const int32_t* parent_labels,
+                     long long parent_row_stride, int ph, int pw, int shift, int n_parent, int32_t* parent_of, long long* parent_rows,
+                     void* hip_stream);
+int cerb_points_knn(const int32_t* xy, int n, int k, int32_t* idx_out, long long* d2_out, void* hip_stream);
+
 /* ---- training augmentations: the shape and input augmentations in front of gen_targets (loader/augs.py lambdas + affine / flip / crop) --------------
  * The host draws every random number (cerberus_amd/augs.py: sample_params) and uploads a few numbers per sample; every call below is a pure function
  * of (input, per-sample parameter arrays), runs the whole batch in ONE launch on hip_stream, allocates nothing and does not synchronise.  Images are
