@@ -9,6 +9,7 @@ Host mirrors of the reference interface (same names / argument meaning):
   cerberus_amd.valid_stats.ValidStats / valid_step_stats / validate <- reference models/run_desc.py:606-747 (ProcStepRawOutput) and :505-565
   cerberus_amd.augs.sample_params / augment_batch / train_batch <- reference loader/augs.py (the lambdas) and the affine / flip / crop steps around them
   cerberus_amd.viz.draw_contours_device / overlay_from_parts / visualize_instances_dict_device <- reference misc/viz_utils.py:150-214 (the overlays)
+  cerberus_amd.rasterize.fill_contours_device / label_maps_from_dict / load_annotations <- (not in the reference) label maps back from contours
 All arithmetic runs in libcerberus_hip.so (include/cerberus_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"
@@ -27,4 +28,8 @@ def __getattr__(name):  # cerberus_amd.ValidStats / valid_step_stats / validate 
         from . import viz
 
         return getattr(viz, name)
+    if name in ("fill_contours_device", "label_maps_from_parts", "label_maps_from_dict", "load_annotations"):
+        from . import rasterize
+
+        return getattr(rasterize, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -22,6 +22,7 @@ EXPORTS = [
     "cerb_aug_warp", "cerb_aug_gaussian_blur", "cerb_aug_median_blur", "cerb_aug_gaussian_noise", "cerb_aug_brightness", "cerb_aug_saturation", "cerb_aug_hue",
     "cerb_aug_contrast", "cerb_aug_channel_sums",
     "cerb_overlay_workspace_bytes", "cerb_overlay_clear", "cerb_overlay_stamp", "cerb_overlay_resolve",
+    "cerb_overlay_fill", "cerb_overlay_labels",
 ]
 
 
@@ -241,6 +242,9 @@ def lib():
                                      C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
     L.cerb_overlay_resolve.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_longlong, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_overlay_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong,
+                                    C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+    L.cerb_overlay_labels.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]
     L.cerb_event_create.argtypes = [C.POINTER(C.c_void_p)]
     L.cerb_event_record.argtypes = [C.c_void_p, C.c_void_p]
     L.cerb_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]

@@ -100,6 +100,11 @@ STATS_OPTIONS = [
                                "ascending id order)"),
     ("--tissue", True, "nuclei", "which <tissue>_mat to score: nuclei | gland | lumen"),
     ("--types", True, None, "number of classes, background included: also report PQ per class 1 .. n-1 and their mean (needs 'inst_type' on the true side)"),
+    ("--pred_dat", True, None, "instead of --pred_dir / --true_dir: the dat/<slide>.dat of run_infer_wsi.py; its contours are filled into a label map on the device "
+                               "(cerberus_amd/rasterize.py) and scored against --true_ann; classes for --types are the instances' 'type' entries; "
+                               "<slide>_stats.csv is written beside the file"),
+    ("--true_ann", True, None, "with --pred_dat: the annotation -- another .dat, a .json of the reference's save_json, a .geojson FeatureCollection (QuPath's "
+                               "export; polygons without holes) or a label-map .npz (keys Nuclei / Gland / Lumen, type_* class maps for --types)"),
 ]
 
 # compute_features.py (not in the reference: its misc/viz_utils.py visualize_graph sketches the gland graph these tables feed)
@@ -110,6 +115,8 @@ FEATURES_OPTIONS = [
     ("--npz", True, None, "a <slide>.npz of run_infer_wsi.py --save_label_maps (keys Nuclei, Gland, Lumen, type_*): gland and lumen maps at the nuclei "
                           "map's resolution or at half of it; the CSVs are written to <directory of the file>/features/"),
     ("--knn", True, "4", "neighbours per gland in the gland table (1 .. 8; 0: none)"),
+    ("--dat", True, None, "a dat/<slide>.dat of run_infer_wsi.py: the label maps are filled from its contours on the device (cerberus_amd/rasterize.py), gland "
+                          "and lumen at half the resolution as the slide driver keeps them; the same CSVs as --npz, written to <directory of the file>/features/"),
 ]
 
 

@@ -9,7 +9,7 @@ int cerb_set_error(const std::string& m) {
     g_err = m;
     return 1;
 }
-extern "C" int cerb_version(void) { return 3; }  // 3: the cerb_overlay_* entries (instance overlays); 2: the cerb_aug_* entries
+extern "C" int cerb_version(void) { return 4; }  // 4: cerb_overlay_fill / _labels (label maps from contours); 3: the cerb_overlay_* entries (instance overlays); 2: the cerb_aug_* entries
 extern "C" const char* cerb_last_error(void) { return g_err.c_str(); }
 std::atomic<long long> g_devbuf_bytes{0};
 extern "C" size_t cerb_device_bytes_held(void) { const long long v = g_devbuf_bytes.load(); return v > 0 ? (size_t)v : 0; }

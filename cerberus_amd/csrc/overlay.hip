@@ -26,8 +26,24 @@
 //                      Painter's order without order: a covered pixel takes max(plane, ordinal) with an integer atomic max.
 //   ov_resolve_kernel  dst = colour[prio - 1] where the plane is non-zero (and names a colour), else src[y / up][x / up].  One thread per output pixel,
 //                      three byte stores: rows may start at any byte (row strides in bytes, padded rows), and the pass moves 7 bytes per pixel.
-// Plain vector loads / stores and integer atomics only; no LDS apart from the 64 skip flags of a wave; all pixel offsets are 64-bit.
+//   ov_fill_kernel     The INTERIOR of the same contours into the same plane (the header's "label maps from contours": even-odd on pixel centres, the
+//                      ray pointing left, rows half-open).  Same groups, same pass 1 (ov_pass1) -- which here also takes every contour's box of
+//                      transformed points (LDS min / max).  The interior of a contour lies in columns xmin .. xmax - 1 and rows ymin .. ymax - 1 (at
+//                      x = xmax every crossing of the row counts, and a closed polygon crosses a row an even number of times); that box, clipped to
+//                      the image, is cut into 64 x 64 cells and the group's (contour, cell) items are dealt round-robin to the gridDim.y waves
+//                      that share the group.  Lane r of a wave owns row y0 + r of the cell as a 64-bit mask in a register.  The wave walks the
+//                      contour's edges 64 at a time: a lane loads one edge and says whether it can matter to this cell (crosses one of its rows,
+//                      not wholly to its right); the ones that do are broadcast one after the other (ballot + shuffle) and every lane whose row
+//                      the edge crosses XORs ~0 << clamp(xc - x0, 0, 64) into its mask -- no LDS and no atomic while accumulating.  xc is the exact
+//                      integer ceiling (a double quotient corrected by integer checks, as ov_isqrt).  Writing: the row masks are broadcast one at
+//                      a time and lane c issues the atomic max for column c, so that one atomic instruction covers one contiguous row segment.
+//                      Every loop is bounded by the clipped box; a wave's time grows with points x cells.
+//   ov_labels_kernel   dst = table[prio - 1] where the plane is non-zero (and names an entry), else `background`: int32, one thread per pixel, 8 bytes
+//                      per pixel.
+// Plain vector loads / stores and integer atomics only; no LDS apart from a wave's 64 skip flags (and, in the fill, its 64 boxes); all pixel offsets
+// are 64-bit.
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include <string>
@@ -112,6 +128,36 @@ __device__ __forceinline__ void ov_locate(i64 incl, i64 s, int& j, i64& k) {
     k = s - (j > 0 ? before : 0);
 }
 
+// inclusive prefix sum of v over the 64 lanes of the wave
+__device__ __forceinline__ i64 ov_incl(i64 v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const i64 a = __shfl_up(v, d);
+        if (lane >= d) v += a;
+    }
+    return v;
+}
+
+// Pass 1 of a 64-contour group: every point through the call's transform, 64 at a time whatever the contours' sizes; bad[j] = 1 for a contour with a
+// coordinate outside the range (every writer stores the same word).  BOX: box[j] = (xmin, xmax, ymin, ymax) of contour j's transformed points as well
+// (preset by the caller; meaningless for a contour marked bad).  Every lane calls it; the caller synchronises before and after.
+template <bool BOX>
+__device__ __forceinline__ void ov_pass1(const int32_t* __restrict__ pts, i64 incl_p, i64 tot_p, i64 off, int lane, int mul, int div, i64 org_x, i64 org_y,
+                                         uint32_t* bad, int (*box)[4]) {
+    for (i64 b0 = 0; b0 < tot_p; b0 += 64) {
+        const i64 s = b0 + lane;
+        int j;
+        i64 k;
+        ov_locate(incl_p, s < tot_p ? s : tot_p - 1, j, k);
+        const i64 joff = __shfl(off, j);
+        if (s < tot_p) {
+            int x, y;
+            if (!ov_point(pts, joff + k, mul, div, org_x, org_y, x, y)) bad[j] = 1;
+            else if (BOX) atomicMin(&box[j][0], x), atomicMax(&box[j][1], x), atomicMin(&box[j][2], y), atomicMax(&box[j][3], y);
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void ov_stamp_kernel(const int32_t* __restrict__ pts, const i64* __restrict__ offsets, const int32_t* __restrict__ counts,
                                                       i64 n, int mul, int div, i64 org_x, i64 org_y, int width, uint32_t first_ordinal,
                                                       uint32_t* __restrict__ plane, int H, int W) {
@@ -124,27 +170,12 @@ __global__ __launch_bounds__(64) void ov_stamp_kernel(const int32_t* __restrict_
     // points read in pass 1: all of them; segments drawn in pass 2: a count of 2 is ONE capsule (its closing segment is the same set)
     const i64 npt = cnt > 0 ? cnt : 0;
     const i64 nseg = cnt == 2 ? 1 : npt;
-    i64 incl_p = npt, incl_s = nseg;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const i64 a = __shfl_up(incl_p, d), b = __shfl_up(incl_s, d);
-        if (lane >= d) incl_p += a, incl_s += b;
-    }
+    const i64 incl_p = ov_incl(npt, lane), incl_s = ov_incl(nseg, lane);
     const i64 tot_p = __shfl(incl_p, 63), tot_s = __shfl(incl_s, 63);
     if (tot_p == 0) return;  // (uniform over the wave)
     bad[lane] = 0;
     __syncthreads();
-    for (i64 b0 = 0; b0 < tot_p; b0 += 64) {
-        const i64 s = b0 + lane;
-        int j;
-        i64 k;
-        ov_locate(incl_p, s < tot_p ? s : tot_p - 1, j, k);
-        const i64 joff = __shfl(off, j);
-        if (s < tot_p) {
-            int x, y;
-            if (!ov_point(pts, joff + k, mul, div, org_x, org_y, x, y)) bad[j] = 1;  // (every writer stores the same word)
-        }
-    }
+    ov_pass1<false>(pts, incl_p, tot_p, off, lane, mul, div, org_x, org_y, bad, nullptr);
     __syncthreads();
     const uint32_t my_bad = bad[lane];
     const int e = (width + 1) >> 1;
@@ -218,6 +249,98 @@ __global__ __launch_bounds__(64) void ov_stamp_kernel(const int32_t* __restrict_
     }
 }
 
+// exact ceil(num / den), den > 0, |num| < 2^44 and |num / den| < 2^22: a double quotient (off by far less than 1) corrected by integer checks
+__device__ __forceinline__ i64 ov_ceil_div(i64 num, i64 den) {
+    i64 c = (i64)ceil((double)num / (double)den);
+    while ((c - 1) * den >= num) --c;
+    while (c * den < num) ++c;
+    return c;
+}
+
+__global__ __launch_bounds__(64) void ov_fill_kernel(const int32_t* __restrict__ pts, const i64* __restrict__ offsets, const int32_t* __restrict__ counts,
+                                                     i64 n, int mul, int div, i64 org_x, i64 org_y, uint32_t first_ordinal, uint32_t* __restrict__ plane,
+                                                     int H, int W) {
+    __shared__ uint32_t bad[64];
+    __shared__ int box[64][4];
+    const int lane = threadIdx.x;
+    const i64 base_c = (i64)blockIdx.x * 64;
+    const i64 ci = base_c + lane;
+    const int cnt = ci < n ? counts[ci] : 0;
+    const i64 off = ci < n ? offsets[ci] : 0;
+    const i64 incl_p = ov_incl(cnt > 0 ? cnt : 0, lane);
+    const i64 tot_p = __shfl(incl_p, 63);
+    if (tot_p == 0) return;  // (uniform over the wave)
+    bad[lane] = 0;
+    box[lane][0] = box[lane][2] = INT_MAX, box[lane][1] = box[lane][3] = INT_MIN;
+    __syncthreads();
+    ov_pass1<true>(pts, incl_p, tot_p, off, lane, mul, div, org_x, org_y, bad, box);
+    __syncthreads();
+    // this lane's contour: the clipped box of its interior and the cells it is cut into (fewer than 3 points, skipped, flat or outside: none)
+    int fx0 = 0, fx1 = -1, fy0 = 0, fy1 = -1, ncx = 0, ncy = 0;
+    if (cnt >= 3 && !bad[lane]) {
+        fx0 = box[lane][0] < 0 ? 0 : box[lane][0], fx1 = box[lane][1] - 1 > W - 1 ? W - 1 : box[lane][1] - 1;
+        fy0 = box[lane][2] < 0 ? 0 : box[lane][2], fy1 = box[lane][3] - 1 > H - 1 ? H - 1 : box[lane][3] - 1;
+        if (fx0 <= fx1 && fy0 <= fy1) ncx = ((fx1 - fx0) >> 6) + 1, ncy = ((fy1 - fy0) >> 6) + 1;
+    }
+    const i64 incl_i = ov_incl((i64)ncx * ncy, lane);
+    const i64 tot_i = __shfl(incl_i, 63);
+    // the group's (contour, cell) items, dealt round-robin to the gridDim.y waves that share the group (each of them has run pass 1 in full)
+    for (i64 t = blockIdx.y; t < tot_i; t += gridDim.y) {
+        int j;
+        i64 k;
+        ov_locate(incl_i, t, j, k);
+        const i64 joff = __shfl(off, j);
+        const int jcnt = __shfl(cnt, j), jncx = __shfl(ncx, j);
+        const int jx0 = __shfl(fx0, j), jx1 = __shfl(fx1, j), jy0 = __shfl(fy0, j), jy1 = __shfl(fy1, j);
+        const int x0 = jx0 + (int)(k % jncx) * 64, y0 = jy0 + (int)(k / jncx) * 64;  // the cell's first column and row
+        const int ylast = y0 + 63 < jy1 ? y0 + 63 : jy1;
+        const int y = y0 + lane;  // this lane's row (rows past ylast are accumulated and never written)
+        unsigned long long mask = 0;
+        for (int e0 = 0; e0 < jcnt; e0 += 64) {
+            const int e = e0 + lane;
+            int ax = 0, ay = 0;
+            if (e < jcnt) ov_point(pts, joff + e, mul, div, org_x, org_y, ax, ay);
+            int bx = __shfl_down(ax, 1), by = __shfl_down(ay, 1);  // the next lane's point is this edge's end, except for lane 63 and the closing edge
+            bool rel = false;
+            if (e < jcnt) {
+                if (lane == 63 || e + 1 == jcnt) ov_point(pts, joff + (e + 1 < jcnt ? e + 1 : 0), mul, div, org_x, org_y, bx, by);
+                if (ay > by) {  // (xc does not depend on the edge's direction)
+                    const int tx = ax, ty = ay;
+                    ax = bx, ay = by, bx = tx, by = ty;
+                }
+                // it can matter to this cell: crosses one of its rows (half-open: a horizontal edge crosses none) and is not wholly to its right
+                rel = ay < by && ay <= ylast && by > y0 && (ax < x0 + 64 || bx < x0 + 64);
+            }
+            unsigned long long todo = __ballot(rel);
+            while (todo) {  // (uniform over the wave)
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const int sax = __shfl(ax, src), say = __shfl(ay, src), sbx = __shfl(bx, src), sby = __shfl(by, src);
+                if (y >= say && y < sby) {
+                    i64 d = 0;  // wholly left of the cell: the whole row toggles
+                    if (sax > x0 || sbx > x0) d = sax + ov_ceil_div((i64)(y - say) * (sbx - sax), sby - say) - x0;
+                    if (d < 64) mask ^= ~0ull << (d < 0 ? 0 : d);
+                }
+            }
+        }
+        const int ncol = jx1 - x0 + 1;  // >= 1; columns past the clipped box are never written
+        if (ncol < 64) mask &= (1ull << ncol) - 1;
+        const uint32_t ord = first_ordinal + (uint32_t)(base_c + j) + 1u;
+        for (int r = 0; r <= ylast - y0; ++r) {
+            const unsigned long long m = (unsigned long long)__shfl((i64)mask, r);
+            if ((m >> lane) & 1) atomicMax(&plane[(size_t)(y0 + r) * W + x0 + lane], ord);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ov_labels_kernel(const int32_t* __restrict__ table, uint32_t n_total, int32_t background, const uint32_t* __restrict__ plane,
+                                                        uint8_t* __restrict__ dst, i64 dst_stride, int H, int W) {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= W) return;
+    const uint32_t pr = plane[(size_t)y * W + x];
+    ((int32_t*)(dst + (i64)y * dst_stride))[x] = (pr != 0 && pr <= n_total) ? table[pr - 1] : background;
+}
+
 __global__ __launch_bounds__(256) void ov_resolve_kernel(const uint8_t* __restrict__ src, i64 src_stride, int up, const uint32_t* __restrict__ colours,
                                                          uint32_t n_total, const uint32_t* __restrict__ plane, uint8_t* __restrict__ dst, i64 dst_stride,
                                                          int H, int W) {
@@ -252,15 +375,24 @@ extern "C" int cerb_overlay_clear(void* ws, size_t ws_bytes, int out_h, int out_
     return 0;
 }
 
+// the checks the two calls that take contours share; `who` names the call in the message
+static int ov_check_contours(const char* who, const void* points, const void* offsets, const void* counts, const void* ws, long long n, int mul, int div,
+                             long long org_x, long long org_y, long long first_ordinal, size_t ws_bytes, int out_h, int out_w) {
+    const std::string w(who);
+    if (!points || !offsets || !counts || !ws || ((uintptr_t)ws & 3) != 0) return cerb_set_error(w + ": null or misaligned pointer");
+    if (ov_bad_size(out_h, out_w)) return cerb_set_error(w + ": image sides must be 1..32768");
+    if (n < 0 || first_ordinal < 0 || first_ordinal > OV_MAX_TOTAL || n > OV_MAX_TOTAL - first_ordinal)
+        return cerb_set_error(w + ": n / first_ordinal negative, or 2^32 - 1 contours and more in total");
+    if (mul < 1 || mul > 16 || div < 1 || div > 4096) return cerb_set_error(w + ": mul (1..16) or div (1..4096) out of range");
+    if (org_x < -(1ll << 40) || org_x > (1ll << 40) || org_y < -(1ll << 40) || org_y > (1ll << 40)) return cerb_set_error(w + ": origin beyond +-2^40");
+    if (ws_bytes < cerb_overlay_workspace_bytes(out_h, out_w)) return cerb_set_error(w + ": workspace too small");
+    return 0;
+}
+
 extern "C" int cerb_overlay_stamp(const int32_t* points, const int64_t* offsets, const int32_t* counts, long long n, int mul, int div, long long org_x,
                                   long long org_y, int width, long long first_ordinal, void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream) {
-    if (!points || !offsets || !counts || !ws || ((uintptr_t)ws & 3) != 0) return cerb_set_error("cerb_overlay_stamp: null or misaligned pointer");
-    if (ov_bad_size(out_h, out_w)) return cerb_set_error("cerb_overlay_stamp: image sides must be 1..32768");
-    if (n < 0 || first_ordinal < 0 || first_ordinal > OV_MAX_TOTAL || n > OV_MAX_TOTAL - first_ordinal)
-        return cerb_set_error("cerb_overlay_stamp: n / first_ordinal negative, or 2^32 - 1 contours and more in total");
-    if (width < 1 || width > 255 || mul < 1 || mul > 16 || div < 1 || div > 4096) return cerb_set_error("cerb_overlay_stamp: width (1..255), mul (1..16) or div (1..4096) out of range");
-    if (org_x < -(1ll << 40) || org_x > (1ll << 40) || org_y < -(1ll << 40) || org_y > (1ll << 40)) return cerb_set_error("cerb_overlay_stamp: origin beyond +-2^40");
-    if (ws_bytes < cerb_overlay_workspace_bytes(out_h, out_w)) return cerb_set_error("cerb_overlay_stamp: workspace too small");
+    if (width < 1 || width > 255) return cerb_set_error("cerb_overlay_stamp: width (1..255) out of range");
+    if (int rc = ov_check_contours("cerb_overlay_stamp", points, offsets, counts, ws, n, mul, div, org_x, org_y, first_ordinal, ws_bytes, out_h, out_w)) return rc;
     if (n == 0) return 0;
     const long long blocks = (n + 63) / 64;  // < 2^26
     // few contours (a tile: a dozen glands of a thousand points each) would leave the chip to one wave per 64 of them: such calls give every group
@@ -283,6 +415,33 @@ extern "C" int cerb_overlay_resolve(const uint8_t* src, long long src_row_stride
     if (ws_bytes < cerb_overlay_workspace_bytes(out_h, out_w)) return cerb_set_error("cerb_overlay_resolve: workspace too small");
     hipLaunchKernelGGL(ov_resolve_kernel, dim3((out_w + 255) / 256, out_h), dim3(256), 0, (hipStream_t)hip_stream, src, (i64)src_row_stride, up, colours,
                        (uint32_t)n_total, (const uint32_t*)ws, dst, (i64)dst_row_stride, out_h, out_w);
+    OV_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cerb_overlay_fill(const int32_t* points, const int64_t* offsets, const int32_t* counts, long long n, int mul, int div, long long org_x,
+                                 long long org_y, long long first_ordinal, void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream) {
+    if (int rc = ov_check_contours("cerb_overlay_fill", points, offsets, counts, ws, n, mul, div, org_x, org_y, first_ordinal, ws_bytes, out_h, out_w)) return rc;
+    if (n == 0) return 0;
+    const long long blocks = (n + 63) / 64;  // < 2^26
+    // as the stamp: a call with few groups (a tile's dozen glands, each a box of many cells) gives every group up to 64 waves, which share its items
+    const long long split = blocks >= OV_FILL_WAVES ? 1 : (OV_FILL_WAVES / blocks > 64 ? 64 : OV_FILL_WAVES / blocks);
+    hipLaunchKernelGGL(ov_fill_kernel, dim3((unsigned)blocks, (unsigned)split), dim3(64), 0, (hipStream_t)hip_stream, points, (const i64*)offsets, counts, (i64)n, mul, div,
+                       (i64)org_x, (i64)org_y, (uint32_t)first_ordinal, (uint32_t*)ws, out_h, out_w);
+    OV_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cerb_overlay_labels(const int32_t* table, long long n_total, int background, const void* ws, size_t ws_bytes, int32_t* dst,
+                                   long long dst_row_stride, int out_h, int out_w, void* hip_stream) {
+    if (!ws || !dst || ((uintptr_t)ws & 3) != 0 || ((uintptr_t)table & 3) != 0 || ((uintptr_t)dst & 3) != 0)
+        return cerb_set_error("cerb_overlay_labels: null or misaligned pointer");
+    if (n_total < 0 || n_total > OV_MAX_TOTAL || (n_total > 0 && !table)) return cerb_set_error("cerb_overlay_labels: n_total negative, 2^32 - 1 and above, or without a table");
+    if (ov_bad_size(out_h, out_w)) return cerb_set_error("cerb_overlay_labels: image sides must be 1..32768");
+    if (dst_row_stride < 4ll * out_w || (dst_row_stride & 3) != 0) return cerb_set_error("cerb_overlay_labels: the row stride is shorter than its row or no multiple of 4");
+    if (ws_bytes < cerb_overlay_workspace_bytes(out_h, out_w)) return cerb_set_error("cerb_overlay_labels: workspace too small");
+    hipLaunchKernelGGL(ov_labels_kernel, dim3((out_w + 255) / 256, out_h), dim3(256), 0, (hipStream_t)hip_stream, table, (uint32_t)n_total, (int32_t)background,
+                       (const uint32_t*)ws, (uint8_t*)dst, (i64)dst_row_stride, out_h, out_w);
     OV_OK(hipGetLastError());
     return 0;
 }

@@ -86,7 +86,7 @@ def _pack_dict(tissue, insts, vi, width=None):
             "colours": np.asarray(cols, np.uint32), "width": int(vi["line_width"] if width is None else width), "mul": 1, "div": 1, "origin": (0, 0)}
 
 
-def _group_to_device(g, dev):
+def _group_to_device(g, dev, who="draw_contours_device"):
     """-> (points int32 [P, 2], offsets int64 [n], counts int32 [n], colours uint32-as-int32 [n]) on dev.  A run that leaves the point list draws nothing:
     host arrays are checked (ValueError), device arrays get their count cleared on the device -- no host wait."""
     import torch
@@ -97,7 +97,7 @@ def _group_to_device(g, dev):
         else:
             a = np.asarray(a)
             if dt == torch.int32 and a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-                raise ValueError("draw_contours_device: a value does not fit int32")
+                raise ValueError("%s: a value does not fit int32" % who)
             t = torch.from_numpy(np.ascontiguousarray(a.astype({torch.int32: np.int32, torch.int64: np.int64}[dt]))).to(dev)
         return t.reshape(shape).contiguous()
 
@@ -109,11 +109,11 @@ def _group_to_device(g, dev):
         col = torch.from_numpy(np.ascontiguousarray(np.asarray(col, dtype=np.uint32)).view(np.int32)).to(dev).reshape(-1)
     n = int(cnts.shape[0])
     if int(offs.shape[0]) != n or int(col.shape[0]) != n:
-        raise ValueError("draw_contours_device: offsets, counts and colours must have one entry per contour")
+        raise ValueError("%s: offsets, counts and colours must have one entry per contour" % who)
     if not any(isinstance(g[k], torch.Tensor) for k in ("points", "offsets", "counts")):
         o, c = np.asarray(g["offsets"], dtype=np.int64).reshape(-1), np.maximum(np.asarray(g["counts"], dtype=np.int64).reshape(-1), 0)
         if n and not bool(((o >= 0) & (o + c <= int(pts.shape[0]))).all()):
-            raise ValueError("draw_contours_device: a contour's run of points leaves the point list")
+            raise ValueError("%s: a contour's run of points leaves the point list" % who)
     else:
         inside = (offs >= 0) & (offs + cnts.clamp(min=0) <= int(pts.shape[0]))
         cnts = torch.where(inside, cnts, torch.zeros_like(cnts))

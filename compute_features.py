@@ -4,8 +4,9 @@ nuclei per class, its lumen fraction and its nearest glands.  Prints one JSON li
 
     python compute_features.py --pred_dir=output/ [--knn=4]        # <pred_dir>/{nuclei,gland,lumen}_mat/<name>.mat of run_infer_tile.py
     python compute_features.py --npz=output/slide.npz [--knn=4]    # the label maps of run_infer_wsi.py --save_label_maps
+    python compute_features.py --dat=output/dat/slide.dat [--knn=4]  # the instance dictionary alone: its contours are filled on the device
 
-Writes <pred_dir>/features/<name>_{nuclei,gland,lumen}.csv (for --npz: features/ beside the file, <name> = the file's stem).  A tissue without a
+Writes <pred_dir>/features/<name>_{nuclei,gland,lumen}.csv (for --npz and --dat: features/ beside the file, <name> = the file's stem).  A tissue without a
 .mat file (or key) is left out.  On a slide the gland and lumen maps may be at half the nuclei map's resolution; any other ratio is refused."""
 import json
 import os
@@ -71,6 +72,28 @@ def _load_npz(path):
     return maps, types
 
 
+def _load_dat(path):
+    """{tissue: CUDA int32 map}, nuclei class vector by id or None -- the maps filled on the device from the dictionary's contours
+    (cerberus_amd/rasterize.py).  The slide driver keeps gland and lumen at half the resolution and stores their contours doubled: when every gland and
+    lumen coordinate is even, those two maps are filled at half the resolution (div = 2), which gives back the driver's own maps."""
+    import numpy as np
+
+    from cerberus_amd.rasterize import dict_tissues, label_maps_from_dict, load_annotations
+
+    d, _ = load_annotations(path)
+    if "proc_dimensions" not in d:
+        sys.exit("%s holds no 'proc_dimensions'" % path)
+    keys = {k.lower(): k for k in dict_tissues(d)}
+    have = [t for t in TISSUES if t in keys]
+    if not have:
+        sys.exit("%s holds none of the keys Nuclei, Gland, Lumen" % path)
+    coarse = [np.asarray(e["contour"]) for t in ("gland", "lumen") if t in keys for e in d[keys[t]].values() if e.get("contour") is not None]
+    half = bool(coarse) and all(not (c & 1).any() for c in coarse)
+    got = label_maps_from_dict(d, tissues=[keys[t] for t in have], div={keys[t]: 2 for t in ("gland", "lumen") if t in keys and half})
+    maps = {t: got[keys[t]][0] for t in have}
+    return maps, (got[keys["nuclei"]][1] if "nuclei" in have else None)
+
+
 def _shift(name, maps):
     """the shift between the nuclei grid and the gland / lumen grid; exits, by name, on maps that do not fit together"""
     from cerberus_amd.inst_features import shift_for
@@ -90,8 +113,8 @@ def _shift(name, maps):
 
 def main(argv=None):
     args = parse("compute_features.py", FEATURES_OPTIONS, argv, version="cerberus_amd compute_features")
-    if bool(args["--pred_dir"]) == bool(args["--npz"]):
-        sys.exit("exactly one of --pred_dir and --npz is required")
+    if sum(bool(args[k]) for k in ("--pred_dir", "--npz", "--dat")) != 1:
+        sys.exit("exactly one of --pred_dir, --npz and --dat is required")
     try:
         k = int(args["--knn"])
     except ValueError:
@@ -108,10 +131,13 @@ def main(argv=None):
         out_dir = os.path.join(args["--pred_dir"], "features")
         jobs = [(name, lambda p=paths: _load_mats(p)) for name, paths in sorted(names.items())]
     else:
-        if not os.path.isfile(args["--npz"]):
-            sys.exit("no such file: %s" % args["--npz"])
-        out_dir = os.path.join(os.path.dirname(os.path.abspath(args["--npz"])), "features")
-        jobs = [(os.path.splitext(os.path.basename(args["--npz"]))[0], lambda: _load_npz(args["--npz"]))]
+        src = args["--npz"] or args["--dat"]
+        if not os.path.isfile(src):
+            sys.exit("no such file: %s" % src)
+        out_dir = os.path.join(os.path.dirname(os.path.abspath(src)), "features")
+        jobs = [(os.path.splitext(os.path.basename(src))[0], (lambda: _load_npz(src)) if args["--npz"] else (lambda: _load_dat(src)))]
+    if args["--dat"] and args["--gpu"]:  # (this loader fills its maps on the device)
+        os.environ.setdefault("HIP_VISIBLE_DEVICES", args["--gpu"].split(",")[0])
     loaded = []
     for name, load in jobs:  # every refusal before the first byte goes to the GPU
         maps, types = load()

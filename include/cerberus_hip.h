@@ -26,7 +26,7 @@ extern "C" {
 typedef struct cerb_net cerb_net;
 #define CERB_ERR_ALLOC 2
 
-int cerb_version(void); /* 3: with the instance overlays (the cerb_overlay entries below); 2: with the training augmentations (cerb_aug); 1 before */
+int cerb_version(void); /* 4: with the polygon fill (cerb_overlay_fill / _labels); 3: with the instance overlays (the cerb_overlay entries below); 2: with the training augmentations (cerb_aug); 1 before */
 const char* cerb_last_error(void);
 
 /* ---- network construction: replaces create_model / NetDesc.__init__ (models/net_desc.py:23-103,203) ----------
@@ -768,6 +768,34 @@ int cerb_overlay_stamp(const int32_t* points, const int64_t* offsets, const int3
                        long long org_y, int width, long long first_ordinal, void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream);
 int cerb_overlay_resolve(const uint8_t* src, long long src_row_stride, int src_h, int src_w, int up, const uint32_t* colours, long long n_total,
                          const void* ws, size_t ws_bytes, uint8_t* dst, long long dst_row_stride, int out_h, int out_w, void* hip_stream);
+
+/* ---- label maps from contours: polygon fill into the overlay's plane (cerberus_amd/rasterize.py) ---------------------------------
+ * The step back from an instance dictionary (closed contours) to an int32 label map.  The project's own definition, in integers throughout:
+ * cv2.drawContours(thickness=FILLED) / fillPoly are not pinned.  Contours, point transform, the skip rule (a contour with any transformed
+ * coordinate outside [-2^20, 2^20] is skipped as a whole -- fill and outline never disagree about which contours exist), plane, ordinals and limits are
+ * the stamp's, above.
+ *
+ * Interior.  Pixel (x, y) is interior to a contour of at least 3 points iff an ODD number of its edges a -> b satisfy both
+ *     min(ay, by) <= y < max(ay, by)                     (half-open: a horizontal edge never counts, a vertex on a pixel row counts once)
+ *     xc <= x,  xc = ax + ceil((y - ay) (bx - ax) / (by - ay))     (the exact integer ceiling, in int64)
+ *   -- the even-odd rule on pixel centres with the ray pointing left; a self-intersecting polygon follows even-odd.  Contours with fewer than 3 points
+ *   have no interior.  cerb_overlay_fill paints the interior alone.
+ * Filled set = interior + the width-1 stroke of the same contour: cerb_overlay_fill and cerb_overlay_stamp(width = 1) with the same first_ordinal, in
+ *   either order.  Because the outline always belongs to the set, the tie rule for pixels exactly on an edge (xc <= x and not xc < x) does not matter:
+ *   such a pixel lies within 1 / 2 of the edge and the stroke covers it.  For a contour made of 8-direction runs (everything cerb_inst_contour_points
+ *   emits) the width-1 stroke is exactly the contour's lattice points, and the filled set of the outer contour of an instance that is one 8-connected
+ *   piece without holes is the instance itself: a dictionary rasterises back to the label map it came from.  Holes (interior rings) do not exist here.
+ * Painter's order.  As the stamp: a filled pixel takes max(plane, ordinal), ordinal = first_ordinal + i + 1.
+ * Labels.  dst[y][x] = table[prio - 1] where prio = plane[y][x] is in 1..n_total, and `background` elsewhere; table is int32 [n_total] and several
+ *   contours may carry one value (the rings of a MultiPolygon; the instances' types for a class map).  dst is int32 with its row stride in BYTES, a
+ *   multiple of 4 (bytes between rows are not touched).
+ * Neither call allocates or synchronises.  Refusals (an error, no launch, nothing written): a null pointer (table may be NULL when n_total is 0) or one
+ *   that is not 4-byte aligned, a side outside 1..32768, mul / div out of range, a workspace smaller than cerb_overlay_workspace_bytes or not 4-byte
+ *   aligned, a negative n or n_total, first_ordinal + n >= 2^32 - 1, a row stride shorter than its row or no multiple of 4. */
+int cerb_overlay_fill(const int32_t* points, const int64_t* offsets, const int32_t* counts, long long n, int mul, int div, long long org_x,
+                      long long org_y, long long first_ordinal, void* ws, size_t ws_bytes, int out_h, int out_w, void* hip_stream);
+int cerb_overlay_labels(const int32_t* table, long long n_total, int background, const void* ws, size_t ws_bytes, int32_t* dst,
+                        long long dst_row_stride, int out_h, int out_w, void* hip_stream);
 
 int cerb_event_create(void** ev);
 int cerb_event_record(void* ev, void* hip_stream);
