@@ -16,11 +16,11 @@ LIB = os.path.join(HERE, "libcerberus_hip.so")
 LIB_DEV = os.path.join(HERE, "libcerberus_hip_dev.so")
 LIB_HOST = os.path.join(HERE, "libcerberus_host.so")
 HOST_SOURCES = ["host_codecs.c"]
-SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip", "conv_wino4p.hip", "net_kernels.hip", "postproc.hip", "slide_kernels.hip", "train_kernels.hip", "head_train.hip", "conv_wgrad.hip", "conv_wgrad_wino.hip", "pack_kernels.hip", "targets.hip", "valid_stats.hip", "jpeg_kernels.hip", "jpeg_encode.hip", "tissue_mask.hip", "inst_metrics.hip", "inst_features.hip", "augs.hip", "overlay.hip", "cerb_api.hip", "cerb_train.hip"]
+SOURCES = ["conv_igemm.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4b.hip", "conv_wino4p.hip", "net_kernels.hip", "pp_label.hip", "pp_nuclei.hip", "pp_gland.hip", "slide_kernels.hip", "train_kernels.hip", "head_train.hip", "conv_wgrad.hip", "conv_wgrad_wino.hip", "pack_kernels.hip", "targets.hip", "valid_stats.hip", "jpeg_kernels.hip", "jpeg_encode.hip", "tissue_mask.hip", "inst_metrics.hip", "inst_features.hip", "augs.hip", "overlay.hip", "cerb_api.hip", "cerb_train.hip"]
 # The translation units that read developer A/B switches (cerb_common.h: cerb_dev_getenv).  The product library compiles them WITHOUT the switches
 # (every one folds to its default); the same units compiled with -DCERB_DEV_SWITCHES, linked with the other units' objects, make
 # libcerberus_hip_dev.so -- loaded only by the A/B tests' child processes (CERB_DEV_LIB=1, cerberus_amd/_lib.py).
-DEV_SOURCES = ["cerb_api.hip", "cerb_train.hip", "postproc.hip", "conv_wino4b.hip", "train_kernels.hip", "net_kernels.hip", "inst_features.hip"]
+DEV_SOURCES = ["cerb_api.hip", "cerb_train.hip", "pp_nuclei.hip", "conv_wino4b.hip", "train_kernels.hip", "net_kernels.hip", "inst_features.hip"]
 # Linked into libcerberus_hip_dev.so ONLY: the test-only entry layer (cerb_dev_* wrappers over single launchers of cerb_net.h, for tests/dev_kernels.py).
 # The product library neither compiles nor exports them (tests/test_abi.py).
 DEV_ONLY_SOURCES = ["dev_entry.hip"]

@@ -1,4 +1,6 @@
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdlib>
 
 // Developer A/B switches (environment variables read inside the schedules: "keep round 4's passes", "one stream", ...).  The PRODUCT library is built
@@ -11,4 +13,13 @@ static inline const char* cerb_dev_getenv(const char* name) {
     (void)name;
     return nullptr;
 #endif
+}
+
+// hipFuncSetAttribute is per device: remember it per device, not per process (a host process may drive several handles)
+static inline bool cerb_attr_needed(bool (&done)[64]) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return true;
+    if (done[dev]) return false;
+    done[dev] = true;
+    return true;
 }

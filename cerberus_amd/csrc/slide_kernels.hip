@@ -12,9 +12,7 @@
 #include <cmath>
 #include <string>
 
-#include "../../include/cerberus_hip.h"
-
-int cerb_set_error(const std::string& m);
+#include "pp_common.h"
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16;
@@ -126,11 +124,6 @@ __global__ void pclass_tissue_kernel(const float* __restrict__ pclass, long long
     }
 }
 
-static unsigned grid_for(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 16) b = 256 * 16;
-    return (unsigned)(b < 1 ? 1 : b);
-}
 #define SK_CHECK()                                                                                    \
     do {                                                                                              \
         hipError_t e_ = hipGetLastError();                                                            \
@@ -393,6 +386,93 @@ extern "C" int cerb_inst_contour_points(const int32_t* labels, long long lab_row
     hipLaunchKernelGGL(inst_contour_kernel<true>, dim3((n_inst + 63) / 64), dim3(64), 0, (hipStream_t)hip_stream, labels, lab_row_stride, h, w, n_inst,
                        table, (int*)nullptr, offsets, points);
     SK_CHECK();
+    return 0;
+}
+
+// =================================================================================================================
+// Which border cv2.findContours(...)[0][0] is, for an instance made of several 8-connected pieces (a lumen cut by its gland's
+// edge, a gland partly overwritten by a later one): OpenCV returns top-level contours most-recently-found first, so element
+// [0] is the outer border of the piece whose first pixel comes LAST in raster order (loader/postproc.py:29-33 takes [0][0]).
+// One union-find pass over "same id, 8-neighbour" links; start[id-1] = max over the pieces of their first pixel.
+// =================================================================================================================
+// IDX = int for maps below 2^31 pixels (4 bytes of workspace per pixel), long long above (8): a 0.5-mpp scan of a large section is 60000 x 50000.
+// (union-find, pix_yx: pp_common.h)
+template <typename IDX>
+__global__ void cc8_init_kernel(const int* __restrict__ lab, long long ls, int H, int W, IDX* __restrict__ L) {
+    const long long n = (long long)H * W;
+    const double invW = 1.0 / (double)W;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        int y, x;
+        pix_yx(p, W, invW, y, x);
+        L[p] = lab[y * ls + x] > 0 ? (IDX)p : (IDX)-1;
+    }
+}
+template <typename IDX>
+__global__ void cc8_merge_kernel(const int* __restrict__ lab, long long ls, int H, int W, IDX* L) {
+    const long long n = (long long)H * W;
+    const double invW = 1.0 / (double)W;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        int y, x;
+        pix_yx(p, W, invW, y, x);
+        const int id = lab[y * ls + x];
+        if (id <= 0) continue;
+        if (x > 0 && lab[y * ls + x - 1] == id) uf_union<IDX>(L, (IDX)p, (IDX)(p - 1));
+        if (y > 0) {
+            const int* up = lab + (y - 1) * ls;
+            if (up[x] == id) uf_union<IDX>(L, (IDX)p, (IDX)(p - W));
+            else {  // the diagonal links only matter when the pixel above does not already join all three
+                if (x > 0 && up[x - 1] == id) uf_union<IDX>(L, (IDX)p, (IDX)(p - W - 1));
+                if (x + 1 < W && up[x + 1] == id) uf_union<IDX>(L, (IDX)p, (IDX)(p - W + 1));
+            }
+        }
+    }
+}
+template <typename IDX>
+__global__ void cc8_flatten_kernel(IDX* L, long long n) {
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        if (L[p] < 0) continue;
+        L[p] = uf_find<IDX>(L, (IDX)p);
+    }
+}
+template <typename IDX>
+__global__ void cc8_last_root_kernel(const int* __restrict__ lab, long long ls, int H, int W, const IDX* __restrict__ L, int n_inst,
+                                     long long* __restrict__ start) {
+    const long long n = (long long)H * W;
+    const double invW = 1.0 / (double)W;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        if (L[p] != (IDX)p) continue;
+        int y, x;
+        pix_yx(p, W, invW, y, x);
+        const int id = lab[y * ls + x];
+        if (id >= 1 && id <= n_inst) atomicMax((unsigned long long*)&start[id - 1], (unsigned long long)p);
+    }
+}
+template <typename IDX>
+static void contour_start_launch(const int32_t* labels, long long ls, int H, int W, int n_inst, long long* start, void* ws, hipStream_t st) {
+    const long long n = (long long)H * W;
+    IDX* L = (IDX*)ws;
+    const unsigned g = grid_for(n);
+    hipLaunchKernelGGL(cc8_init_kernel<IDX>, dim3(g), dim3(256), 0, st, labels, ls, H, W, L);
+    hipLaunchKernelGGL(cc8_merge_kernel<IDX>, dim3(g), dim3(256), 0, st, labels, ls, H, W, L);
+    hipLaunchKernelGGL(cc8_flatten_kernel<IDX>, dim3(g), dim3(256), 0, st, L, n);
+    hipLaunchKernelGGL(cc8_last_root_kernel<IDX>, dim3(g), dim3(256), 0, st, labels, ls, H, W, (const IDX*)L, n_inst, start);
+}
+extern "C" size_t cerb_inst_contour_start_workspace_bytes(int H, int W) {
+    const long long n = (long long)(H > 0 ? H : 0) * (W > 0 ? W : 0);
+    return (size_t)n * (n >= (1ll << 31) ? 8 : 4);
+}
+extern "C" int cerb_inst_contour_start(const int32_t* labels, long long lab_row_stride, int H, int W, int n_inst, long long* start, void* ws,
+                                       size_t ws_bytes, void* hip_stream) {
+    if (!labels || !start || !ws || H <= 0 || W <= 0 || n_inst < 0) return cerb_set_error("cerb_inst_contour_start: bad arguments");
+    const bool wide = (long long)H * W >= (1ll << 31);
+    if (ws_bytes < cerb_inst_contour_start_workspace_bytes(H, W))
+        return cerb_set_error("cerb_inst_contour_start: workspace too small (4 bytes per pixel, 8 for maps of 2^31 pixels and more)");
+    if (n_inst == 0) return 0;
+    hipStream_t st = (hipStream_t)hip_stream;
+    PP_OK(hipMemsetAsync(start, 0, (size_t)n_inst * 8, st));
+    if (wide) contour_start_launch<long long>(labels, lab_row_stride, H, W, n_inst, start, ws, st);
+    else contour_start_launch<int>(labels, lab_row_stride, H, W, n_inst, start, ws, st);
+    KCHECK();
     return 0;
 }
 

@@ -17,7 +17,7 @@
 // Squared distances are integers, the two-smallest reduction is a per-pixel gather over the label list: no float atomics, no order
 // dependence -- the label list's ORDER (atomic slot counters) changes between runs, the multiset each pixel reduces does not.
 //
-// Why not postproc.hip's labeller: its predicate is a byte plane compared with one value and it labels ONE map per call with tile-local
+// Why not pp_label.hip's labeller: its predicate is a byte plane compared with one value and it labels ONE map per call with tile-local
 // LDS passes tuned for slide-sized maps; here the predicate is "equal non-zero id", the maps are a few hundred pixels on a side and there
 // are N x heads of them per call.  The union-find itself (atomicMin on roots, root = smallest raster index) is the same scheme.
 #include "cerb_net.h"

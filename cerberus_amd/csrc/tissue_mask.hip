@@ -1,5 +1,5 @@
 // Tissue mask of a slide thumbnail on the device: the pixel stages of reference misc/utils.py:195-244 (stain_entropy_otsu; the morphology chain of
-// get_tissue_mask lives beside the labelling kernels it reuses, postproc.hip: cerb_tissue_morphology) and of the third-party routines they call
+// get_tissue_mask is at the end of this file: cerb_tissue_morphology, on the labeller of pp_label.hip) and of the third-party routines they call
 // (skimage.color.rgb2hed, skimage.filters.rank.entropy over disk(4), numpy.histogram behind skimage.filters.threshold_otsu).  Byte and integer work
 // plus table look-ups of doubles: LDS / latency bound, no MFMA.
 //
@@ -24,14 +24,7 @@
 
 #include <string>
 
-#include "../../include/cerberus_hip.h"
-
-int cerb_set_error(const std::string& m);  // cerb_api.hip
-#define TM_OK(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return cerb_set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+#include "pp_common.h"
 
 namespace {
 
@@ -223,7 +216,7 @@ extern "C" size_t cerb_tissue_workspace_bytes(int h, int w) {
 extern "C" int cerb_tissue_hed(const uint8_t* rgb, long long row_stride, int h, int w, const double* lut, uint8_t* planes_out, void* hip_stream) {
     if (!rgb || !lut || !planes_out || tm_bad_size(h, w) || row_stride < 3ll * w) return cerb_set_error("cerb_tissue_hed: bad arguments");
     hipLaunchKernelGGL(tm_hed_kernel, dim3(tm_grid((long long)h * w)), dim3(256), 0, (hipStream_t)hip_stream, rgb, row_stride, h, w, lut, planes_out);
-    TM_OK(hipGetLastError());
+    KCHECK();
     return 0;
 }
 
@@ -237,22 +230,102 @@ extern "C" int cerb_tissue_entropy(const uint8_t* planes, int h, int w, const do
     const dim3 grid((w + TM_TW - 1) / TM_TW, (h + TM_TH - 1) / TM_TH);
     hipLaunchKernelGGL(tm_entropy_kernel, grid, dim3(TM_NT), 0, st, planes, h, w, term_table, ent_out, part);
     hipLaunchKernelGGL(tm_minmax_kernel, dim3(1), dim3(256), 0, st, (const double*)part, tm_blocks(h, w), minmax_out);
-    TM_OK(hipGetLastError());
+    KCHECK();
     return 0;
 }
 
 extern "C" int cerb_tissue_histogram(const double* ent, int h, int w, const double* edges257, int64_t* counts256_out, void* hip_stream) {
     if (!ent || !edges257 || !counts256_out || tm_bad_size(h, w)) return cerb_set_error("cerb_tissue_histogram: bad arguments");
     hipStream_t st = (hipStream_t)hip_stream;
-    TM_OK(hipMemsetAsync(counts256_out, 0, 256 * sizeof(int64_t), st));
+    PP_OK(hipMemsetAsync(counts256_out, 0, 256 * sizeof(int64_t), st));
     hipLaunchKernelGGL(tm_hist_kernel, dim3(tm_grid((long long)h * w)), dim3(256), 0, st, ent, (long long)h * w, edges257, (unsigned long long*)counts256_out);
-    TM_OK(hipGetLastError());
+    KCHECK();
     return 0;
 }
 
 extern "C" int cerb_tissue_threshold(const double* ent, int h, int w, double thr, uint8_t* mask_out, void* hip_stream) {
     if (!ent || !mask_out || tm_bad_size(h, w)) return cerb_set_error("cerb_tissue_threshold: bad arguments");
     hipLaunchKernelGGL(tm_threshold_kernel, dim3(tm_grid((long long)h * w)), dim3(256), 0, (hipStream_t)hip_stream, ent, (long long)h * w, thr, mask_out);
-    TM_OK(hipGetLastError());
+    KCHECK();
+    return 0;
+}
+
+// =================================================================================================================
+// Tissue-mask morphology (misc/utils.py:216-235 `morphology`, the second half of get_tissue_mask :238-244):
+//     binary_erosion(disk(3)) -> remove_small_holes(2000) -> remove_small_objects(2000) -> binary_dilation(disk(3)) -> remove_small_holes(2000)
+//     -> binary_fill_holes, connectivity 1 throughout.
+// The erosion and the dilation are scipy.ndimage's (misc/utils.py:16-19), whose border_value defaults to 0: pixels outside the image count as CLEAR
+// for both, so the erosion removes a 3-pixel rim of anything that touches the image border.  remove_small_objects drops 4-connected components with
+// area < min_size; remove_small_holes is the same on the complement -- border-touching background included, so a mask of fewer than 2000 pixels
+// always ends full.  binary_fill_holes sets the background components that do not reach the image border.  Labelling and areas are
+// pp_label.hip's (pp_ccl_run); the other stages are here.
+// =================================================================================================================
+// disk(3): dx^2 + dy^2 <= 9, 29 pixels.  ERODE: set iff every footprint pixel is inside the image and set; else (dilation): set iff one is.
+template <bool ERODE>
+__global__ void tm_morph_disk3_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int H, int W) {
+    const long long n = (long long)H * W;
+    const double invW = 1.0 / (double)W;
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) {
+        int y, x;
+        pix_yx(p, W, invW, y, x);
+        bool r = ERODE;
+        for (int dy = -3; dy <= 3; ++dy) {
+            const int hw = dy == 0 ? 3 : (dy == 3 || dy == -3) ? 0 : 2;
+            const int yy = y + dy;
+            for (int dx = -hw; dx <= hw; ++dx) {
+                const int xx = x + dx;
+                const bool v = yy >= 0 && yy < H && xx >= 0 && xx < W && in[(long long)yy * W + xx] != 0;
+                r = ERODE ? (r && v) : (r || v);
+            }
+        }
+        out[p] = r ? 1 : 0;
+    }
+}
+// pixels of colour `val` whose component (L: flattened roots, area at the roots) is smaller than min_size take the other colour
+__global__ void tm_flip_small_kernel(uint8_t* __restrict__ m, uint8_t val, const int* __restrict__ L, const int* __restrict__ area, int min_size, int n) {
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x)
+        if (m[p] == val && area[L[p]] < min_size) m[p] = val ? 0 : 1;
+}
+// flag[root] = 1 for the background components that reach the image border (flag zeroed by the caller; every writer stores the same value)
+__global__ void tm_border_bg_kernel(const uint8_t* __restrict__ m, const int* __restrict__ L, int* __restrict__ flag, int H, int W) {
+    const int per = 2 * (H + W);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < per; i += gridDim.x * blockDim.x) {
+        const long long p = perimeter_pixel(i, H, W);
+        if (!m[p]) flag[L[p]] = 1;
+    }
+}
+__global__ void tm_fill_holes_kernel(const uint8_t* __restrict__ m, const int* __restrict__ L, const int* __restrict__ flag, uint8_t* __restrict__ out, int n) {
+    for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < n; p += (long long)gridDim.x * blockDim.x) out[p] = (m[p] || !flag[L[p]]) ? 1 : 0;
+}
+static int tm_remove_small(uint8_t* m, uint8_t val, int* L, int* area, int min_size, int H, int W, hipStream_t st) {
+    const int n = H * W;
+    PP_OK(hipMemsetAsync(area, 0, (size_t)n * 4, st));
+    if (pp_ccl_run(m, val, L, H, W, st, area)) return 1;
+    hipLaunchKernelGGL(tm_flip_small_kernel, dim3(grid_for(n)), dim3(256), 0, st, m, val, (const int*)L, (const int*)area, min_size, n);
+    KCHECK();
+    return 0;
+}
+extern "C" int cerb_tissue_morphology(const uint8_t* mask_in, int H, int W, uint8_t* mask_out, void* ws, size_t ws_bytes, void* hip_stream) {
+    if (int rc = pp_check_map("cerb_tissue_morphology", mask_in && mask_out && ws, H, W, ws_bytes, cerb_tissue_workspace_bytes(H, W))) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int n = H * W;
+    Carve cv{(char*)ws, ws_bytes};
+    int* L = (int*)cv.take((size_t)n * 4);
+    int* area = (int*)cv.take((size_t)n * 4);  // component areas; then the border flags of the hole filling
+    uint8_t* a = (uint8_t*)cv.take(n);
+    uint8_t* b = (uint8_t*)cv.take(n);
+    if (!b) return cerb_set_error("cerb_tissue_morphology: workspace carve failed");
+    const unsigned g = grid_for(n);
+    const int min_size = 2000;  // misc/utils.py:224-230
+    hipLaunchKernelGGL(tm_morph_disk3_kernel<true>, dim3(g), dim3(256), 0, st, mask_in, a, H, W);
+    if (tm_remove_small(a, 0, L, area, min_size, H, W, st)) return 1;  // remove_small_holes
+    if (tm_remove_small(a, 1, L, area, min_size, H, W, st)) return 1;  // remove_small_objects
+    hipLaunchKernelGGL(tm_morph_disk3_kernel<false>, dim3(g), dim3(256), 0, st, (const uint8_t*)a, b, H, W);
+    if (tm_remove_small(b, 0, L, area, min_size, H, W, st)) return 1;  // remove_small_holes
+    if (pp_ccl_run(b, 0, L, H, W, st)) return 1;                       // binary_fill_holes
+    PP_OK(hipMemsetAsync(area, 0, (size_t)n * 4, st));
+    hipLaunchKernelGGL(tm_border_bg_kernel, dim3(nblk(2 * ((long long)H + W), 256)), dim3(256), 0, st, (const uint8_t*)b, (const int*)L, area, H, W);
+    hipLaunchKernelGGL(tm_fill_holes_kernel, dim3(g), dim3(256), 0, st, (const uint8_t*)b, (const int*)L, (const int*)area, mask_out, n);
+    KCHECK();
     return 0;
 }

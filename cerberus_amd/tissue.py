@@ -12,7 +12,7 @@
 
   stain_entropy_otsu,  the mask generator the reference's docstring promises for a slide without a mask file (infer/wsi.py:509; misc/utils.py:
   morphology,          195-244), which its command line never reaches: stain bytes, local entropy, histogram, threshold and the morphology chain
-  get_tissue_mask      are HIP kernels (csrc/tissue_mask.hip, csrc/postproc.hip), the two tables and Otsu's arithmetic on 256 counts are numpy
+  get_tissue_mask      are HIP kernels (csrc/tissue_mask.hip, over the labeller of csrc/pp_label.hip), the two tables and Otsu's arithmetic on 256 counts are numpy
 
 Without a mask the reference builds an all-ones mask at slide resolution -> one region = the whole slide; that case never
 materialises a mask here (region_lab NULL).  There is no CPU fallback: every map stays in HBM."""

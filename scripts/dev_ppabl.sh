@@ -1,11 +1,11 @@
 #!/bin/bash
-# developer ablation: rebuild postproc.hip with -D flags on the GPU box and report per-kernel times of the nuclei pipeline at 8192^2
+# developer ablation: rebuild pp_nuclei.hip (the nuclei path; the labeller is pp_label.hip) with -D flags on the GPU box and report per-kernel times of the nuclei pipeline at 8192^2
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 IFS=';'
 for FL in ${CERB_VARIANTS:-""}; do
   unset IFS
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FL -c cerberus_amd/csrc/postproc.hip -o cerberus_amd/csrc/postproc.o || exit 1
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FL -c cerberus_amd/csrc/pp_nuclei.hip -o cerberus_amd/csrc/pp_nuclei.o || exit 1
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o cerberus_amd/libcerberus_hip.so cerberus_amd/csrc/*.o || exit 1
   echo "=== flags: [$FL]"
   python scripts/dev_pp_nuclei_only.py ${PP_SIDE:-8192} 2>&1 | tail -1

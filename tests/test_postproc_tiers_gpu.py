@@ -1,4 +1,4 @@
-"""The post-processing kernels (csrc/postproc.hip) on engineered maps (tests/pp_maps.py): every watershed flood tier, every cap of the tier rule
+"""The post-processing kernels (csrc/pp_label.hip, pp_nuclei.hip, pp_gland.hip) on engineered maps (tests/pp_maps.py): every watershed flood tier, every cap of the tier rule
 and one past it, ties, labelling seams and holes, the min-area thresholds at equality, and tiny maps -- bit for bit against the C oracle, scipy or
 the CPU tier predictor.  tests/test_pp_maps_host.py checks, without a GPU, that the maps reach what they are named after."""
 import hashlib

@@ -1,5 +1,5 @@
 """The tissue-mask generator on the device (cerberus_amd/tissue.py: stain_entropy_otsu, morphology, get_tissue_mask; csrc/tissue_mask.hip and the
-morphology entry of csrc/postproc.hip) against the reference's own values (misc/utils.py:195-244 through tests/tools/gen_golden_tissue_mask.py ->
+morphology entry at its end) against the reference's own values (misc/utils.py:195-244 through tests/tools/gen_golden_tissue_mask.py ->
 tests/golden/tissue_mask.npz), and `run_infer_wsi.py --auto_mask` against the `--msk_dir` run on the mask it saved.
 
 Entropy bound: a value is the sum of at most 49 table terms of magnitude <= 0.531 (max of -p log2 p), each added with about one ulp (1.1e-16) of

@@ -2,7 +2,7 @@
  * watershed result does not depend on skimage's heap-layout tie order.
  *
  * sim_watershed floods every 4-connected mask component on its own with the total order (value, age, pixel index) -- what
- * the HIP kernels of cerberus_amd/csrc/postproc.hip do -- and raises `ambiguous` by the same rules; the checker
+ * the HIP kernels of cerberus_amd/csrc/pp_nuclei.hip do -- and raises `ambiguous` by the same rules; the checker
  * (tests/tools/dev_tie_rule_fuzz.py) compares it with the oracle's literal global binary heap (oracle/postproc_ref.c) on
  * tie-heavy maps: every map with ambiguous == 0 must be identical.
  *
