@@ -583,13 +583,12 @@ int train_wino4_slot(cerb_net* net, const std::string& name, PackedConv& cm, int
     if (!slot) {
         auto rit = net->raw.find(name);
         if (rit == net->raw.end()) return fail("conv " + name + ": no raw weights for the F(4x4) transform");
-        const size_t nw = (size_t)cm.cout * cm.cin * 9, nu = (size_t)cm.cout * cm.cin * 36;
+        const size_t nu = (size_t)cm.cout * cm.cin * 36;
         void* d = nullptr;
         HIP_OK(hipMalloc(&d, (size_t)cm.groups * nu * 4));
         net->dev_allocs.push_back(d);
         net->dev_alloc_bytes.push_back((size_t)cm.groups * nu * 4);
         slot = (float*)d;
-        (void)nw;
         HIP_OK(cerb_launch_pack_wino4(rit->second.w, slot, dgrad ? cm.cin : cm.cout, dgrad ? cm.cout : cm.cin, dgrad, w4b, cm.groups, st));
     }
     *out = slot;
@@ -603,137 +602,97 @@ static constexpr int kPlanarLowest = 0;
 // included.  Stages 1..3 (128^2 x 64, 64^2 x 128, 32^2 x 256) win in every round; stage 4 (16^2 x 512: one block per image, so 16 block pairs x 8 blocks of
 // 64 output channels = 128 items for 256 workgroups, where conv_wino4b's one-block items fill them) loses 0.33 ms and stays on NHWC.
 static constexpr int kEncPlanarStages = 0x7;
-// Profile families of the tile-planar launches, by decoder level (bench.py's table keeps the levels apart).  The two lowest levels' names start with
-// "conv_wino4_planar", not "conv_wino4p": tests/test_net_gpu.py counts the families that start with "conv_wino4p" (and the entry passes named exactly
-// "upsample2_add_planar") and expects the two last levels' four (two) launches.
-static const char* const kPlanarFamily[4] = {"conv_wino4_planar<f4x4,16x16x2,eighth-res>", "conv_wino4_planar<f4x4,16x16x2,quarter-res>",
-                                             "conv_wino4p<f4x4,16x16x2,planar,half-res>", "conv_wino4p<f4x4,16x16x2,planar>"};
-// The encoder's planar stages: the names start with "conv_wino4" (bench.py prices executed FLOPs by that prefix) and with none of the decoder's prefixes.
-static const char* const kEncPlanarFamily = "conv_wino4_enc<f4x4,16x16x2>";
-static const char* const kEncPlanarFamilyRes = "conv_wino4_enc<f4x4,16x16x2,res>";
+// Profile families of the planar levels' entry passes, by decoder level (bench.py's table keeps the levels apart; tests/test_net_gpu.py counts the
+// entry passes named exactly "upsample2_add_planar" and expects the two last levels' two).  The convolutions' families: conv_plan.h.
 static const char* const kPlanarEntryFamily[4] = {"upsample2_add_planar<eighth-res>", "upsample2_add_planar<quarter-res>", "upsample2_add_planar", "upsample2_add_planar"};
 
-int run_conv(cerb_net* net, const std::string& name, const float* in, const float* prev, const float* resid, float* out, int N,
-             int H, int W, int relu, int mode, long long in_gs, long long prev_gs, hipStream_t st, double* macs,
-             const int* roi, long long planar_out_gs) {  // planar_out_gs > 0: in / out are tile-planar (conv_wino4p.hip)
-    auto it = net->conv.find(name);
-    if (it == net->conv.end()) return fail("internal: conv " + name + " not packed");
-    const PackedConv& c = it->second;
-    struct BnReq {  // the request holds for this call only
-        cerb_net* n;
-        ~BnReq() { n->conv_bn_part = nullptr; }
-    } bn_req{net};
-    net->conv_bn_bpg = 0;
-    ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.in = in; p.prev = prev; p.wpack = c.w; p.bias = c.b; p.resid = resid; p.out = out;
-    p.N = N; p.H = H; p.W = W; p.Cin = c.cin; p.Cout = c.cout;
-    p.Ho = (c.stride == 2) ? H / 2 : H;
-    p.Wo = (c.stride == 2) ? W / 2 : W;
-    p.relu = relu;
-    p.groups = c.groups;
-    p.in_gs = in_gs; p.prev_gs = prev_gs;
-    p.w_gs = (long long)c.cout * c.cin * c.ks * c.ks;
-    p.bias_gs = c.cout;
-    p.resid_gs = 0;
-    p.out_gs = (long long)N * p.Ho * p.Wo * c.cout;
-    p.pk_off = net->packed_items ? 0 : 1;
-    if (macs) {
-        *macs += (double)c.groups * N * p.Ho * p.Wo * (double)c.cout * c.cin * c.ks * c.ks;
-        if (!out) return 0;
+// F(4x4,3x3) weights of an inference handle in conv_wino4.hip's (w4b = 0) or conv_wino4b.hip's layout: transformed on the host from the BN-folded
+// copy at first use, in the kernel's per-wave layout, and uploaded
+static int infer_wino4_slot(cerb_net* net, PackedConv& cm, int w4b, float** out) {
+    float*& slot = w4b ? cm.wino4b : cm.wino4;
+    if (!slot) {
+        std::vector<float> w4;
+        for (int g = 0; g < cm.groups; ++g) pack_wino4(cm.host_w.data() + (size_t)g * cm.cout * cm.cin * 9, cm.cout, cm.cin, &w4, w4b);
+        void* d = nullptr;
+        HIP_OK(hipMalloc(&d, w4.size() * 4));
+        net->dev_allocs.push_back(d);
+        net->dev_alloc_bytes.push_back(w4.size() * 4);
+        HIP_OK(hipMemcpy(d, w4.data(), w4.size() * 4, hipMemcpyHostToDevice));
+        slot = (float*)d;
     }
-    const double fl = 2.0 * (double)c.groups * N * p.Ho * p.Wo * (double)c.cout * c.cin * c.ks * c.ks;
-    // conv_algo 6 (default): F(4x4,3x3) for maps of at least 16 x 16 pixels -- conv_wino4b.hip (one-block items, 32-channel chunks) up to
-    // 64 x 64, conv_wino4.hip (two-block items, half the weight traffic) above; F(2x2,3x3) for smaller maps, where a 16 x 16 block would
-    // be mostly padding.  Measured per layer on a batch of 32 256-pixel tiles (scripts/dev_conv_layers.py): 16^2 x 512 ch 0.115 / 0.21 /
-    // 0.146 ms (4b / 4 / F(2x2)), 64^2 x 128 ch 0.131 / 0.138 / 0.158, 256^2 x 64 ch x 5 decoders 2.63 / 2.52 / 3.28.  The rule looks at
-    // the layer's geometry only -- never at the batch size or the region of interest -- so that a tile's values do not depend on what it
-    // is batched with (sharded == unsharded, cropped == full stay bitwise, tests/test_drivers_gpu.py, test_net_gpu.py).
-    const long long map_px = (long long)p.Ho * p.Wo;
-    const bool use_w4 = net->conv_algo == 5 || net->conv_algo == 7 || (net->conv_algo == 6 && map_px >= 256);
-    const bool planar = planar_out_gs > 0;
-    static const long long w4b_max_px = [] {  // developer A/B only (scripts/gpu_session_r04c.sh): where conv_wino4b hands over to conv_wino4
-        const char* e = cerb_dev_getenv("CERB_W4B_MAX_PX");
-        return e ? atoll(e) : 4096ll;
-    }();
-    const bool w4b = !planar && (net->conv_algo == 7 || (net->conv_algo == 6 && map_px <= w4b_max_px)) && c.cin % 64 == 0;
-    const bool enc_planar = planar && net->planar_level == 4;  // an encoder stage: the only planar launches with a residual, and with stride-2 producers
-    if (enc_planar && c.stride == 2) {  // the stage's entry: NHWC in, tile-planar out (conv_igemm.hip)
-        if (resid || mode != 0 || !net->fold_bn) return fail("internal: conv " + name + " cannot store tile-planar");
-        p.out_gs = planar_out_gs;
-        p.pl_byp = cerb_planar_blocks(p.Ho);
-        p.pl_bxp = cerb_planar_blocks(p.Wo);
-        const std::string kn = "conv_igemm_planar<ks" + std::to_string(c.ks) + ",s2" + (p.Wo < 32 ? ",16x16>" : ",8x32>");
-        if (prof_begin(net, name, kn, fl, st)) return 1;
-        HIP_OK(cerb_launch_conv(p, c.ks, c.stride, mode, st));
-        if (prof_end(net, st)) return 1;
-        return 0;
-    }
-    if (planar && !(use_w4 && c.wino && mode == 0 && net->fold_bn && (!resid || enc_planar))) return fail("internal: conv " + name + " cannot take the planar path");
-    if (use_w4 && c.wino && mode == 0 && (!it->second.host_w.empty() || !net->fold_bn)) {
-        PackedConv& cm = it->second;
-        float* train_slot = nullptr;
-        if (!net->fold_bn && train_wino4_slot(net, name, cm, w4b ? 1 : 0, 0, st, &train_slot)) return 1;
-        float*& slot4 = !net->fold_bn ? train_slot : (w4b ? cm.wino4b : cm.wino4);
-        if (!slot4) {  // first use: F(4x4,3x3) filter transform on the host, the kernel's per-wave layout, upload
-            std::vector<float> w4;
-            for (int g = 0; g < cm.groups; ++g) pack_wino4(cm.host_w.data() + (size_t)g * cm.cout * cm.cin * 9, cm.cout, cm.cin, &w4, w4b ? 1 : 0);
-            void* d = nullptr;
-            HIP_OK(hipMalloc(&d, w4.size() * 4));
-            net->dev_allocs.push_back(d);
-            net->dev_alloc_bytes.push_back(w4.size() * 4);
-            HIP_OK(hipMemcpy(d, w4.data(), w4.size() * 4, hipMemcpyHostToDevice));
-            slot4 = (float*)d;
-        }
-        p.wpack = slot4;
-        p.w_gs = (long long)c.cout * c.cin * 36;
-        double fl_done = fl;
-        if (roi && roi[1] > roi[0] && roi[3] > roi[2]) {  // region of interest: report the work of the 16 x 16 blocks that run
-            p.roi_y0 = roi[0]; p.roi_y1 = roi[1]; p.roi_x0 = roi[2]; p.roi_x1 = roi[3];
-            const double ty = (roi[1] + 15) / 16 - roi[0] / 16, tx = (roi[3] + 15) / 16 - roi[2] / 16;
-            fl_done = fl * (ty * 16.0 * tx * 16.0) / ((double)p.Ho * p.Wo);
-        }
-        if (planar) {
-            p.out_gs = planar_out_gs;
-            p.level_tag = enc_planar ? (resid ? 4 : 3) : net->planar_level == 3 ? 1 : net->planar_level == 2 ? 0 : 2;
-            p.pl_byp = cerb_planar_blocks(p.Ho);
-            p.pl_bxp = cerb_planar_blocks(p.Wo);
-        }
-        if (prof_begin(net, name, enc_planar ? (resid ? kEncPlanarFamilyRes : kEncPlanarFamily) : planar ? kPlanarFamily[net->planar_level & 3] : w4b ? (cerb_wino4b_packed(p) ? (resid ? "conv_wino4b<f4x4,16t,res>" : "conv_wino4b<f4x4,16t>") : (resid ? "conv_wino4b<f4x4,16x16,res>" : "conv_wino4b<f4x4,16x16>")) : (resid ? "conv_wino4<f4x4,16x16x2,res>" : "conv_wino4<f4x4,16x16x2>"), fl_done, st)) return 1;
-        if (net->conv_bn_part && !planar && !resid && !(roi && roi[1] > roi[0] && roi[3] > roi[2])) {
-            p.bn_part = net->conv_bn_part;
-            net->conv_bn_bpg = w4b ? cerb_wino4b_bn_blocks(p) : N * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
-        }
-        HIP_OK(planar ? cerb_launch_wino4p(p, st) : w4b ? cerb_launch_wino4b(p, st) : cerb_launch_wino4(p, st));
-        if (prof_end(net, st)) return 1;
-        return 0;
-    }
-    if (net->conv_algo && c.wino && mode == 0) {
-        if (train_wino2_fresh(net, name, it->second, 0, st)) return 1;
-        p.wpack = c.wino;
-        p.w_gs = (long long)c.cout * c.cin * 16;
-        double fl_done = fl;
-        if (roi && roi[1] > roi[0] && roi[3] > roi[2]) {  // region of interest: report the work of the items that run (8 x 16 px each)
-            p.roi_y0 = roi[0]; p.roi_y1 = roi[1]; p.roi_x0 = roi[2]; p.roi_x1 = roi[3];
-            const double ty = (roi[1] + 7) / 8 - roi[0] / 8, tx = (roi[3] + 15) / 16 - roi[2] / 16;
-            fl_done = fl * (ty * 8.0 * tx * 16.0) / ((double)p.Ho * p.Wo);
-        }
-        if (prof_begin(net, name, resid ? "conv_wino<f2x2,8x16,res>" : "conv_wino<f2x2,8x16>", fl_done, st)) return 1;
-        HIP_OK(cerb_launch_wino(p, st));
-        if (prof_end(net, st)) return 1;
-        return 0;
-    }
-    const std::string kn = "conv_igemm<ks" + std::to_string(c.ks) + ",s" + std::to_string(c.stride) + ",mode" + std::to_string(mode) +
-                           (p.Wo < 32 ? ",16x16>" : ",8x32>");
-    if (prof_begin(net, name, kn, fl, st)) return 1;
-    HIP_OK(cerb_launch_conv(p, c.ks, c.stride, mode, st));
-    if (prof_end(net, st)) return 1;
+    *out = slot;
     return 0;
 }
 
-static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st, double* macs) {
+int run_conv(cerb_net* net, const std::string& name, const ConvCall& a, hipStream_t st) {
+    auto it = net->conv.find(name);
+    if (it == net->conv.end()) return fail("internal: conv " + name + " not packed");
+    PackedConv& c = it->second;
+    if (a.bn_bpg) *a.bn_bpg = 0;
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    p.in = a.in; p.prev = a.prev; p.wpack = c.w; p.bias = c.b; p.resid = a.resid; p.out = a.out;
+    p.N = a.N; p.H = a.H; p.W = a.W; p.Cin = c.cin; p.Cout = c.cout;
+    p.Ho = (c.stride == 2) ? a.H / 2 : a.H;
+    p.Wo = (c.stride == 2) ? a.W / 2 : a.W;
+    p.relu = a.relu;
+    p.groups = c.groups;
+    p.in_gs = a.in_gs; p.prev_gs = a.prev_gs;
+    p.w_gs = (long long)c.cout * c.cin * c.ks * c.ks;
+    p.bias_gs = c.cout;
+    p.resid_gs = 0;
+    p.out_gs = (long long)a.N * p.Ho * p.Wo * c.cout;
+    p.pk_off = net->packed_items ? 0 : 1;
+    const bool planar = a.planar_out_gs > 0, enc = a.site == kSiteEncoder;
+    const ConvLayer layer{net->conv_algo, c.ks, c.stride, c.cin, c.cout, p.Ho, p.Wo, c.wino != nullptr, a.mode, planar, !net->fold_bn};
+    const ConvKernel k = conv_plan(layer);
+    // a tile-planar launch names its site; only an encoder stage has residuals, and stride-2 producers (which take none)
+    if (planar && (k == CONV_NONE || a.site < 0 || a.site > kSiteEncoder || ((a.resid || c.stride == 2) && !enc) || (a.resid && c.stride == 2)))
+        return fail("internal: conv " + name + " cannot take the planar path");
+    if (planar) {
+        p.out_gs = a.planar_out_gs;
+        if (k == CONV_WINO4P) p.level_tag = enc ? (a.resid ? 4 : 3) : a.site == 3 ? 1 : a.site == 2 ? 0 : 2;
+        p.pl_byp = cerb_planar_blocks(p.Ho);
+        p.pl_bxp = cerb_planar_blocks(p.Wo);
+    }
+    const bool f4 = k == CONV_WINO4 || k == CONV_WINO4B || k == CONV_WINO4P;
+    if (f4) {
+        float* w4 = nullptr;
+        if (net->fold_bn ? infer_wino4_slot(net, c, k == CONV_WINO4B, &w4) : train_wino4_slot(net, name, c, k == CONV_WINO4B, 0, st, &w4)) return 1;
+        p.wpack = w4;
+        p.w_gs = (long long)c.cout * c.cin * 36;
+    } else if (k == CONV_WINO2) {
+        if (train_wino2_fresh(net, name, c, 0, st)) return 1;
+        p.wpack = c.wino;
+        p.w_gs = (long long)c.cout * c.cin * 16;
+    }
+    const double fl = 2.0 * (double)c.groups * a.N * p.Ho * p.Wo * (double)c.cout * c.cin * c.ks * c.ks;
+    double fl_done = fl;
+    const bool roi = (f4 || k == CONV_WINO2) && a.roi && a.roi[1] > a.roi[0] && a.roi[3] > a.roi[2];
+    if (roi) {  // region of interest: report the work of the items that run (F(4x4): 16 x 16 blocks, F(2x2): 8 x 16 px)
+        p.roi_y0 = a.roi[0]; p.roi_y1 = a.roi[1]; p.roi_x0 = a.roi[2]; p.roi_x1 = a.roi[3];
+        const int ih = f4 ? 16 : 8;
+        const double ty = (a.roi[1] + ih - 1) / ih - a.roi[0] / ih, tx = (a.roi[3] + 15) / 16 - a.roi[2] / 16;
+        fl_done = fl * (ty * ih * tx * 16.0) / ((double)p.Ho * p.Wo);
+    }
+    if (prof_begin(net, name, conv_family(k, layer, a.resid != nullptr, k == CONV_WINO4B && cerb_wino4b_packed(p), a.site), fl_done, st)) return 1;
+    if (a.bn_part && a.bn_bpg && conv_has_bn_stats(k) && !a.resid && !roi) {
+        p.bn_part = a.bn_part;
+        *a.bn_bpg = k == CONV_WINO4B ? cerb_wino4b_bn_blocks(p) : a.N * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16);
+    }
+    switch (k) {
+        case CONV_WINO4P: HIP_OK(cerb_launch_wino4p(p, st)); break;
+        case CONV_WINO4B: HIP_OK(cerb_launch_wino4b(p, st)); break;
+        case CONV_WINO4: HIP_OK(cerb_launch_wino4(p, st)); break;
+        case CONV_WINO2: HIP_OK(cerb_launch_wino(p, st)); break;
+        default: HIP_OK(cerb_launch_conv(p, c.ks, c.stride, a.mode, st)); break;
+    }
+    return prof_end(net, st);
+}
+
+
+static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st) {
     g_call_stream = st;
-    const bool dry = (macs != nullptr) && (io->tiles == nullptr) && (io->tiles_f32 == nullptr);
     const int N = io->n, H = io->h, W = io->w;
     if (N <= 0 || H <= 0 || W <= 0 || (H % 16) || (W % 16)) return fail("cerb_net_forward: tile H,W must be positive multiples of 16");
     const int out_h = io->out_h > 0 ? io->out_h : H, out_w = io->out_w > 0 ? io->out_w : W;
@@ -744,7 +703,7 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
     // Which decoder levels keep their three private tensors in the tile-planar layout (conv_wino4p.hip), on the default algorithms with folded
     // BatchNorm: the two last levels (64 channels) when their maps reach past conv_wino4b's range, and below them the levels kPlanarLowest.. (any
     // Cin % 16 == 0, Cout % 64 == 0) whose maps hold at least one 16 x 16 block.  A planar level may only feed a planar one, so a level is planar
-    // only if every level above it is.  One predicate for the allocation and the loop.
+    // only if every level above it is.  Decided once per call, for the allocation and the loop.
     // Measured per launch on the headline's batch (32 tiles of 256^2, five decoders; profiles/decoder_low_levels_planar_ab.txt), conv_wino4b on NHWC ->
     // conv_wino4p on planar, ms: dec.1.0 (64^2, 128 -> 64) 0.539 -> 0.478, dec.1.1 (64 -> 64) 0.286 -> 0.251, its entry pass 0.100 -> 0.108;
     // dec.0.0 (32^2, 256 -> 128) 0.504 -> 0.449, dec.0.1 (128 -> 128: 640 items on 256 workgroups, 2.5 rounds) 0.269 -> 0.270, its entry pass
@@ -753,62 +712,17 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
         const char* e = cerb_dev_getenv("CERB_PLANAR_LOWEST");
         return e ? atoi(e) : kPlanarLowest;
     }();
-    auto level_is_planar = [&](int u) {
-        if (dry || !net->planar || !net->fold_bn || net->conv_algo != 6 || net->head_algo < 1) return false;
-        for (int v = 3; v >= u; --v) {
-            if (v < planar_lowest) return false;
-            auto c0 = net->conv.find("dec." + std::to_string(v) + ".0"), c1 = net->conv.find("dec." + std::to_string(v) + ".1");
-            if (c0 == net->conv.end() || c1 == net->conv.end() || !c0->second.wino || !c1->second.wino) return false;
-            const long long px = (long long)hs[3 - v] * ws[3 - v];
-            if ((hs[3 - v] & 3) || (ws[3 - v] & 3)) return false;  // whole 4 x 4 tiles (the lowest level of a 208-pixel tile is 26 x 26)
-            const bool ok = v >= 2 ? px >= 4096 && c0->second.cin == 64 && c0->second.cout == 64 && c1->second.cout == 64
-                                   : px >= 256 && c0->second.cin % 16 == 0 && c0->second.cout % 64 == 0 && c1->second.cin == c0->second.cout && c1->second.cout % 64 == 0;
-            if (!ok) return false;
-        }
-        return true;
-    };
-    if (!dry) {
-        if (net->x0.ensure((size_t)N * H * W * 64 * 4, guard) || net->pool.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard)) return fail_alloc();
-        for (int i = 1; i < 5; ++i)
-            if (net->x[i].ensure((size_t)N * hs[i] * ws[i] * kFilters[i] * 4, guard)) return fail_alloc();
-        if (net->ta.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard) || net->tb.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard) ||
-            net->cm.ensure((size_t)N * hs[4] * ws[4] * 256 * 4, guard))
-            return fail_alloc();
-        if (D) {
-            // dsum / dmid hold the entry sum and the first conv's output of a level that runs NHWC (per decoder 32^2 x 256, 64^2 x 128, and -- when the
-            // tile-planar levels are off -- 128^2 x 64, 256^2 x 64), dout[u] its second conv's output; the planar levels have their own buffers, so with
-            // them on (the default) only the two coarse levels count here: 8 GB less per handle at 32 tiles of 256^2 (a first attempt in this
-            // round faulted on a wrong channel count in its own formula, not on a kernel reaching past its tensor: sized from the packed convolutions'
-            // channel counts below, every fixture and geometry of the GPU suite runs).  CERB_LEGACY_WS=1: everything at last-level size, as before.
-            static const bool exact_ws = cerb_dev_getenv("CERB_LEGACY_WS") == nullptr;
-            size_t need_sum = 0, need_mid = 0;
-            const int oc[4] = {128, 64, 64, 64};
-            for (int u = 0; u < 4; ++u) {
-                if (exact_ws && level_is_planar(u)) continue;
-                const std::string n0 = "dec." + std::to_string(u) + ".0";
-                auto c0 = net->conv.find(n0);
-                const size_t px = (size_t)D * N * hs[3 - u] * ws[3 - u];
-                need_sum = std::max(need_sum, px * (size_t)(c0 != net->conv.end() ? c0->second.cin : 256) * 4);
-                need_mid = std::max(need_mid, px * (size_t)(c0 != net->conv.end() ? c0->second.cout : 256) * 4);
-            }
-            if (!exact_ws) need_sum = need_mid = D * (size_t)N * H * W * 64 * 4;
-            if (net->dmid.ensure(need_mid, guard)) return fail_alloc();
-            if (net->conv_algo && net->dsum.ensure(need_sum, guard)) return fail_alloc();
-            for (int u = 0; u < 4; ++u) {
-                if (exact_ws && level_is_planar(u)) continue;  // its outputs live in the planar buffers
-                if (net->dout[u].ensure(D * (size_t)N * hs[3 - u] * ws[3 - u] * oc[u] * 4, guard)) return fail_alloc();
-            }
-        }
-    }
-    // ---- encoder ----------------------------------------------------------------------------------------------
-    if (macs) *macs += (double)N * H * W * 64.0 * 147.0;
-    if (!dry) {
-        StemParams sp;
-        sp.tiles = io->tiles; sp.tiles_f32 = io->tiles ? nullptr : io->tiles_f32; sp.wpack = net->stem_w; sp.bias = net->stem_b; sp.out = net->x0.p; sp.N = N; sp.H = H; sp.W = W; sp.relu = 1;
-        sp.tiles_x = sp.tiles_y = 0;
-        if (prof_begin(net, "stem", "stem_conv7x7", 2.0 * N * H * W * 64.0 * 147.0, st)) return 1;
-        HIP_OK(cerb_launch_stem(sp, st));
-        if (prof_end(net, st)) return 1;
+    const bool planar_on = net->planar && net->fold_bn && net->conv_algo == 6;
+    bool level_is_planar[4] = {false, false, false, false};
+    for (int v = 3; v >= 0 && v >= planar_lowest && planar_on && net->head_algo >= 1; --v) {
+        auto c0 = net->conv.find("dec." + std::to_string(v) + ".0"), c1 = net->conv.find("dec." + std::to_string(v) + ".1");
+        if (c0 == net->conv.end() || c1 == net->conv.end() || !c0->second.wino || !c1->second.wino) break;
+        const long long px = (long long)hs[3 - v] * ws[3 - v];
+        if ((hs[3 - v] & 3) || (ws[3 - v] & 3)) break;  // whole 4 x 4 tiles (the lowest level of a 208-pixel tile is 26 x 26)
+        const bool ok = v >= 2 ? px >= kW4bMaxPx && c0->second.cin == 64 && c0->second.cout == 64 && c1->second.cout == 64
+                               : px >= kF4MinPx && c0->second.cin % 16 == 0 && c0->second.cout % 64 == 0 && c1->second.cin == c0->second.cout && c1->second.cout % 64 == 0;
+        if (!ok) break;
+        level_is_planar[v] = true;
     }
     // Which residual stages keep conv1's output, conv2's output and the block identity in the tile-planar layout and run their stride-1 3x3 convolutions
     // on conv_wino4p.hip (two blocks per weight register): inference on the default algorithms with folded BatchNorm only.  Decided
@@ -819,58 +733,80 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
         const char* e = cerb_dev_getenv("CERB_ENC_PLANAR");
         return e ? atoi(e) : kEncPlanarStages;
     }();
-    auto encoder_stage_is_planar = [&](int li) {
-        if (dry || !net->planar || !net->fold_bn || net->conv_algo != 6 || !((enc_mask >> li) & 1)) return false;
+    bool encoder_stage_is_planar[4];
+    for (int li = 0; li < 4; ++li) {
         const int hh = hs[li + 1], ww = ws[li + 1], planes = kFilters[li + 1];
-        if ((hh & 15) || (ww & 15) || hh < 16 || ww < 16 || planes % 64) return false;
-        for (int b = 0; b < kLayers[li]; ++b)
-            for (int j = 1; j <= 2; ++j) {
+        bool ok = planar_on && ((enc_mask >> li) & 1) && !((hh & 15) || (ww & 15) || hh < 16 || ww < 16 || planes % 64);
+        for (int b = 0; ok && b < kLayers[li]; ++b)
+            for (int j = 1; ok && j <= 2; ++j) {
                 auto c = net->conv.find("backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b) + ".conv" + std::to_string(j));
-                if (c == net->conv.end()) return false;
-                if (c->second.stride == 1 && (!c->second.wino || c->second.host_w.empty() || c->second.cin % 16)) return false;
+                ok = c != net->conv.end() && !(c->second.stride == 1 && (!c->second.wino || c->second.host_w.empty() || c->second.cin % 16));
             }
-        return true;
-    };
-    if (!dry) {
-        if (encoder_stage_is_planar(0)) {
-            if (net->enc_a[0].ensure(1, N, hs[1], ws[1], 64, st)) return fail_alloc();
-            if (prof_begin(net, "maxpool", "maxpool3x3s2_planar", 0.0, st)) return 1;
-            HIP_OK(cerb_launch_maxpool_planar(net->x0.p, net->enc_a[0].b.p, N, H, W, 64, st));
-            if (prof_end(net, st)) return 1;
-        } else {
-            if (prof_begin(net, "maxpool", "maxpool3x3s2", 0.0, st)) return 1;
-            HIP_OK(cerb_launch_maxpool(net->x0.p, net->pool.p, N, H, W, 64, st));
-            if (prof_end(net, st)) return 1;
-        }
+        encoder_stage_is_planar[li] = ok;
     }
-    float* cur = dry ? nullptr : net->pool.p;
+    if (net->x0.ensure((size_t)N * H * W * 64 * 4, guard) || net->pool.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard)) return fail_alloc();
+    for (int i = 1; i < 5; ++i)
+        if (net->x[i].ensure((size_t)N * hs[i] * ws[i] * kFilters[i] * 4, guard)) return fail_alloc();
+    if (net->ta.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard) || net->tb.ensure((size_t)N * hs[1] * ws[1] * 64 * 4, guard) ||
+        net->cm.ensure((size_t)N * hs[4] * ws[4] * 256 * 4, guard))
+        return fail_alloc();
+    if (D) {
+        // dsum / dmid hold the entry sum and the first conv's output of a level that runs NHWC (per decoder 32^2 x 256, 64^2 x 128, and -- when the
+        // tile-planar levels are off -- 128^2 x 64, 256^2 x 64), dout[u] its second conv's output; the planar levels have their own buffers, so with
+        // them on (the default) only the two coarse levels count here: 8 GB less per handle at 32 tiles of 256^2 (a first attempt in this
+        // round faulted on a wrong channel count in its own formula, not on a kernel reaching past its tensor: sized from the packed convolutions'
+        // channel counts below, every fixture and geometry of the GPU suite runs).
+        size_t need_sum = 0, need_mid = 0;
+        const int oc[4] = {128, 64, 64, 64};
+        for (int u = 0; u < 4; ++u) {
+            if (level_is_planar[u]) continue;  // its tensors live in the planar buffers
+            auto c0 = net->conv.find("dec." + std::to_string(u) + ".0");
+            const size_t px = (size_t)D * N * hs[3 - u] * ws[3 - u];
+            need_sum = std::max(need_sum, px * (size_t)(c0 != net->conv.end() ? c0->second.cin : 256) * 4);
+            need_mid = std::max(need_mid, px * (size_t)(c0 != net->conv.end() ? c0->second.cout : 256) * 4);
+        }
+        if (net->dmid.ensure(need_mid, guard)) return fail_alloc();
+        if (net->conv_algo && net->dsum.ensure(need_sum, guard)) return fail_alloc();
+        for (int u = 0; u < 4; ++u)
+            if (!level_is_planar[u] && net->dout[u].ensure(D * (size_t)N * hs[3 - u] * ws[3 - u] * oc[u] * 4, guard)) return fail_alloc();
+    }
+    // ---- encoder ----------------------------------------------------------------------------------------------
+    {
+        StemParams sp;
+        sp.tiles = io->tiles; sp.tiles_f32 = io->tiles ? nullptr : io->tiles_f32; sp.wpack = net->stem_w; sp.bias = net->stem_b; sp.out = net->x0.p; sp.N = N; sp.H = H; sp.W = W; sp.relu = 1;
+        sp.tiles_x = sp.tiles_y = 0;
+        PROF("stem", "stem_conv7x7", 2.0 * N * H * W * 64.0 * 147.0, HIP_OK(cerb_launch_stem(sp, st)));
+    }
+    if (encoder_stage_is_planar[0]) {
+        if (net->enc_a[0].ensure(1, N, hs[1], ws[1], 64, st)) return fail_alloc();
+        PROF("maxpool", "maxpool3x3s2_planar", 0.0, HIP_OK(cerb_launch_maxpool_planar(net->x0.p, net->enc_a[0].b.p, N, H, W, 64, st)));
+    } else {
+        PROF("maxpool", "maxpool3x3s2", 0.0, HIP_OK(cerb_launch_maxpool(net->x0.p, net->pool.p, N, H, W, 64, st)));
+    }
+    float* cur = net->pool.p;
     int inpl = 64;
     for (int li = 0; li < 4; ++li) {
         const int planes = kFilters[li + 1];
         const int Hi = (li == 0) ? hs[1] : hs[li], Wi = (li == 0) ? ws[1] : ws[li];  // input resolution of this layer
-        if (encoder_stage_is_planar(li)) {
+        const int hh = hs[li + 1], ww = ws[li + 1];
+        if (encoder_stage_is_planar[li]) {
             // conv1 -> B, conv2(B) + identity(A) -> A in place (conv_wino4p.hip: every element of the residual is read by the lane that writes it); block 0
             // of the stages 2..4 fills B and A from the NHWC input through the stride-2 convolutions' planar epilogue, stage 1's A is the pooled map
             PlanarBuf &ba = net->enc_a[li], &bb = net->enc_b[li];
-            const int hh = hs[li + 1], ww = ws[li + 1];
             if (ba.ensure(1, N, hh, ww, planes, st) || bb.ensure(1, N, hh, ww, planes, st)) return fail_alloc();
-            const int keep_level = net->planar_level;
-            net->planar_level = 4;
-            struct Restore { cerb_net* n; int v; ~Restore() { n->planar_level = v; } } restore{net, keep_level};
             for (int b = 0; b < kLayers[li]; ++b) {
                 const std::string p = "backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b);
                 if (b == 0 && li > 0) {
-                    if (run_conv(net, p + ".conv1", cur, nullptr, nullptr, bb.b.p, N, Hi, Wi, 1, 0, 0, 0, st, macs, nullptr, bb.gs())) return 1;
-                    if (run_conv(net, p + ".downsample", cur, nullptr, nullptr, ba.b.p, N, Hi, Wi, 0, 0, 0, 0, st, macs, nullptr, ba.gs())) return 1;
-                } else if (run_conv(net, p + ".conv1", ba.b.p, nullptr, nullptr, bb.b.p, N, hh, ww, 1, 0, ba.gs(), 0, st, macs, nullptr, bb.gs())) {
+                    if (run_conv(net, p + ".conv1", {.in = cur, .out = bb.b.p, .N = N, .H = Hi, .W = Wi, .relu = 1, .planar_out_gs = bb.gs(), .site = kSiteEncoder}, st)) return 1;
+                    if (run_conv(net, p + ".downsample", {.in = cur, .out = ba.b.p, .N = N, .H = Hi, .W = Wi, .planar_out_gs = ba.gs(), .site = kSiteEncoder}, st)) return 1;
+                } else if (run_conv(net, p + ".conv1", {.in = ba.b.p, .out = bb.b.p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = ba.gs(), .planar_out_gs = bb.gs(), .site = kSiteEncoder}, st)) {
                     return 1;
                 }
-                if (run_conv(net, p + ".conv2", bb.b.p, nullptr, ba.b.p, ba.b.p, N, hh, ww, 1, 0, bb.gs(), 0, st, macs, nullptr, ba.gs())) return 1;
+                if (run_conv(net, p + ".conv2", {.in = bb.b.p, .resid = ba.b.p, .out = ba.b.p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = bb.gs(), .planar_out_gs = ba.gs(), .site = kSiteEncoder}, st))
+                    return 1;
             }
             // the stage's exit: its consumers (the next stage's stride-2 convolutions, conv_map, Patch-Class, the decoder's skips, io->feats) read NHWC
-            if (prof_begin(net, "backbone.layer" + std::to_string(li + 1) + ".exit", "planar_to_nhwc", 0.0, st)) return 1;
-            HIP_OK(cerb_launch_planar_to_nhwc(ba.b.p, net->x[li + 1].p, N, hh, ww, planes, st));
-            if (prof_end(net, st)) return 1;
+            PROF("backbone.layer" + std::to_string(li + 1) + ".exit", "planar_to_nhwc", 0.0, HIP_OK(cerb_launch_planar_to_nhwc(ba.b.p, net->x[li + 1].p, N, hh, ww, planes, st)));
             cur = net->x[li + 1].p;
             inpl = planes;
             continue;
@@ -878,35 +814,31 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
         for (int b = 0; b < kLayers[li]; ++b) {
             const std::string p = "backbone.layer" + std::to_string(li + 1) + "." + std::to_string(b);
             const int stride = (b == 0 && li > 0) ? 2 : 1;
-            const int hin = (b == 0) ? Hi : hs[li + 1], win = (b == 0) ? Wi : ws[li + 1];
-            float* t1 = dry ? nullptr : net->ta.p;
-            // block output: ping-pong between tb and x[li+1]; make the LAST block of the layer land in x[li+1]
-            const bool last = (b == kLayers[li] - 1);
-            float* outb = dry ? nullptr : (((kLayers[li] - 1 - b) % 2 == 0) ? net->x[li + 1].p : net->tb.p);
-            (void)last;
+            const int hin = (b == 0) ? Hi : hh, win = (b == 0) ? Wi : ww;
+            float* t1 = net->ta.p;
+            // block output: ping-pong between tb and x[li+1]; the LAST block of the layer lands in x[li+1]
+            float* outb = ((kLayers[li] - 1 - b) % 2 == 0) ? net->x[li + 1].p : net->tb.p;
             const float* idt = cur;
-            if (run_conv(net, p + ".conv1", cur, nullptr, nullptr, t1, N, hin, win, 1, 0, 0, 0, st, macs)) return 1;
+            if (run_conv(net, p + ".conv1", {.in = cur, .out = t1, .N = N, .H = hin, .W = win, .relu = 1}, st)) return 1;
             if (stride != 1 || inpl != planes) {
                 // downsample(x): 1x1 stride-2 conv + BN, written to dmid-free scratch: reuse pool buffer (dead after layer1.0)
-                float* ds = dry ? nullptr : net->pool.p;
-                if (run_conv(net, p + ".downsample", cur, nullptr, nullptr, ds, N, hin, win, 0, 0, 0, 0, st, macs)) return 1;
-                idt = ds;
+                if (run_conv(net, p + ".downsample", {.in = cur, .out = net->pool.p, .N = N, .H = hin, .W = win}, st)) return 1;
+                idt = net->pool.p;
             }
-            if (run_conv(net, p + ".conv2", t1, nullptr, idt, outb, N, hs[li + 1], ws[li + 1], 1, 0, 0, 0, st, macs)) return 1;
+            if (run_conv(net, p + ".conv2", {.in = t1, .resid = idt, .out = outb, .N = N, .H = hh, .W = ww, .relu = 1}, st)) return 1;
             cur = outb;
             inpl = planes;
         }
     }
-    if (run_conv(net, "conv_map", dry ? nullptr : net->x[4].p, nullptr, nullptr, dry ? nullptr : net->cm.p, N, hs[4], ws[4], 0, 0, 0, 0, st, macs)) return 1;
+    if (run_conv(net, "conv_map", {.in = net->x[4].p, .out = net->cm.p, .N = N, .H = hs[4], .W = ws[4]}, st)) return 1;
 
     const long long tile_stride = io->tile_stride ? io->tile_stride : (long long)out_h * out_w;
     const long long row_stride = io->row_stride ? io->row_stride : out_w;
     // ---- Patch-Class ------------------------------------------------------------------------------------------
     if (net->pc_idx >= 0) {
-        if (macs) *macs += (double)N * (512.0 * 256 + 256.0 * net->dec[net->pc_idx].out_ch);
         const bool want = io->out && io->out[net->pc_idx];
         const bool wantl = io->logits && io->logits[net->pc_idx];
-        if (!dry && (want || wantl)) {
+        if (want || wantl) {
             PatchClassParams pp;
             memset(&pp, 0, sizeof(pp));
             pp.x4 = net->x[4].p; pp.bn1_s = net->pc_bn1s; pp.bn1_b = net->pc_bn1b; pp.w1t = net->pc_w1t; pp.b1 = net->pc_b1;
@@ -916,15 +848,13 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             pp.logits = wantl ? io->logits[net->pc_idx] : nullptr;
             pp.out = want ? (float*)io->out[net->pc_idx] : nullptr;
             pp.tile_off = io->tile_off; pp.tile_stride = tile_stride; pp.row_stride = row_stride;
-            if (prof_begin(net, "patch_class", "patch_class", 2.0 * N * (512.0 * 256 + 256.0 * pp.out_ch), st)) return 1;
-            HIP_OK(cerb_launch_patch_class(pp, st));
-            if (prof_end(net, st)) return 1;
+            PROF("patch_class", "patch_class", 2.0 * N * (512.0 * 256 + 256.0 * pp.out_ch), HIP_OK(cerb_launch_patch_class(pp, st)));
         }
     }
     // ---- dense decoders (all decoders of a level in ONE grouped launch) ---------------------------------------
     if (D) {
-        const float* skips[4] = {dry ? nullptr : net->x[3].p, dry ? nullptr : net->x[2].p, dry ? nullptr : net->x[1].p, dry ? nullptr : net->x0.p};
-        const float* prev = dry ? nullptr : net->cm.p;
+        const float* skips[4] = {net->x[3].p, net->x[2].p, net->x[1].p, net->x0.p};
+        const float* prev = net->cm.p;
         long long prev_gs = 0;  // conv_map output is shared by every decoder
         const int oc[4] = {128, 64, 64, 64};
         // Regions of interest (crop_rois below): with a centre crop smaller than the tile (the reference's default 448 -> 144 keeps
@@ -938,7 +868,7 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
                 if (io->logits[k]) return true;
             return false;
         }();
-        const bool use_roi = !dry && net->crop_roi && (net->conv_algo == 1 || net->conv_algo >= 5) && !any_logits && (out_h < H || out_w < W);
+        const bool use_roi = net->crop_roi && (net->conv_algo == 1 || net->conv_algo >= 5) && !any_logits && (out_h < H || out_w < W);
         if (use_roi) {
             int y0 = (int)((H - out_h) * 0.5), x0 = (int)((W - out_w) * 0.5), y1 = y0 + out_h, x1 = x0 + out_w;
             // A Winograd tile mixes its WHOLE input patch into every output (the contributions of the pixels a 3x3 filter does not touch
@@ -971,27 +901,23 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             // whole lines, nothing masks an edge.  Same arithmetic in the same order: bit-identical to the NHWC path (cerb_net_set_planar(0)).
             // The level below (same 64 channels at half the resolution) does the same when its maps are above conv_wino4b's range, and hands
             // its output to the last level's up-sampling in that layout.
-            const bool lvl_planar = level_is_planar(u);
-            if (lvl_planar) {
+            const int* r_sum = use_roi ? roi_sum[u] : nullptr;
+            const int* r_mid = use_roi ? roi_mid[u] : nullptr;
+            const int* r_out = use_roi ? roi_out[u] : nullptr;
+            if (level_is_planar[u]) {
                 // two buffers per planar level: the entry sum is dead once the first conv has read it, so the second conv writes its output there
                 // (a third buffer of 8.6 GB at 64 tiles of 256^2 held it before); same geometry, same zero ring
-                PlanarBuf &bs = u == 3 ? net->psum : u == 2 ? net->psum2 : u == 1 ? net->psum1 : net->psum0;
-                PlanarBuf &bm = u == 3 ? net->pmid : u == 2 ? net->pmid2 : u == 1 ? net->pmid1 : net->pmid0;
+                PlanarBuf &bs = net->dec_sum[u], &bm = net->dec_mid[u];
                 // Below the two last levels the entry sum is wider than the level's output (256 -> 128, 128 -> 64 channels): another plane count moves
                 // every block, guard ring included, so an output written over the sum would leave the next call's ring dirty -- those levels keep a
                 // third buffer (a tenth of the last level's size), the 64 -> 64 levels reuse the sum buffer as before.
                 const int cout1 = net->conv[n1].cout;
-                PlanarBuf& bo = cout1 == cin0 ? bs : u == 1 ? net->pout1 : net->pout0;
+                PlanarBuf& bo = cout1 == cin0 ? bs : net->dec_out[u];
                 if (bs.ensure((int)D, N, hh, ww, cin0, st) || bm.ensure((int)D, N, hh, ww, cmid, st) || (&bo != &bs && bo.ensure((int)D, N, hh, ww, cout1, st)))
                     return fail_alloc();
-                if (prof_begin(net, n0 + ".up", kPlanarEntryFamily[u], 0.0, st)) return 1;
-                HIP_OK(cerb_launch_upsample2_add_planar(skips[u], prev, bs.b.p, (int)D, N, hh, ww, cin0, prev_gs, bs.gs(), use_roi ? roi_sum[u] : nullptr, prev_planar ? 1 : 0, st));
-                if (prof_end(net, st)) return 1;
-                net->planar_level = u;
-                if (run_conv(net, n0, bs.b.p, nullptr, nullptr, bm.b.p, N, hh, ww, 1, 0, bs.gs(), 0, st, macs, use_roi ? roi_mid[u] : nullptr, bm.gs()))
-                    return 1;
-                if (run_conv(net, n1, bm.b.p, nullptr, nullptr, bo.b.p, N, hh, ww, 1, 0, bm.gs(), 0, st, macs, use_roi ? roi_out[u] : nullptr, bo.gs()))
-                    return 1;
+                PROF(n0 + ".up", kPlanarEntryFamily[u], 0.0, HIP_OK(cerb_launch_upsample2_add_planar(skips[u], prev, bs.b.p, (int)D, N, hh, ww, cin0, prev_gs, bs.gs(), r_sum, prev_planar ? 1 : 0, st)));
+                if (run_conv(net, n0, {.in = bs.b.p, .out = bm.b.p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = bs.gs(), .roi = r_mid, .planar_out_gs = bm.gs(), .site = u}, st)) return 1;
+                if (run_conv(net, n1, {.in = bm.b.p, .out = bo.b.p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = bm.gs(), .roi = r_out, .planar_out_gs = bo.gs(), .site = u}, st)) return 1;
                 if (u == 3) feat_planar = true;
                 prev = bo.b.p;
                 prev_gs = bo.gs();
@@ -999,19 +925,13 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
                 continue;
             }
             if (prev_planar) return fail("internal: a tile-planar decoder level feeds an NHWC one");
-            if (net->conv_algo && net->conv[n0].wino && !dry) {
+            if (net->conv_algo && net->conv[n0].wino) {
                 // skip + upsample2x(prev) as one HBM pass, then the Winograd conv over the materialised sum
-                if (prof_begin(net, n0 + ".up", "upsample2_add", 0.0, st)) return 1;
-                HIP_OK(cerb_launch_upsample2_add(skips[u], prev, net->dsum.p, (int)D, N, hh, ww, cin0, prev_gs, use_roi ? roi_sum[u] : nullptr, st));
-                if (prof_end(net, st)) return 1;
-                if (run_conv(net, n0, net->dsum.p, nullptr, nullptr, net->dmid.p, N, hh, ww, 1, 0, (long long)N * hh * ww * cin0, 0, st, macs,
-                             use_roi ? roi_mid[u] : nullptr))
-                    return 1;
-            } else if (run_conv(net, n0, skips[u], prev, nullptr, dry ? nullptr : net->dmid.p, N, hh, ww, 1, 1, 0, prev_gs, st, macs)) return 1;
-            if (run_conv(net, n1, dry ? nullptr : net->dmid.p, nullptr, nullptr, dry ? nullptr : net->dout[u].p, N, hh, ww, 1, 0,
-                         (long long)N * hh * ww * cmid, 0, st, macs, use_roi ? roi_out[u] : nullptr))
-                return 1;
-            prev = dry ? nullptr : net->dout[u].p;
+                PROF(n0 + ".up", "upsample2_add", 0.0, HIP_OK(cerb_launch_upsample2_add(skips[u], prev, net->dsum.p, (int)D, N, hh, ww, cin0, prev_gs, r_sum, st)));
+                if (run_conv(net, n0, {.in = net->dsum.p, .out = net->dmid.p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = (long long)N * hh * ww * cin0, .roi = r_mid}, st)) return 1;
+            } else if (run_conv(net, n0, {.in = skips[u], .prev = prev, .out = net->dmid.p, .N = N, .H = hh, .W = ww, .relu = 1, .mode = 1, .prev_gs = prev_gs}, st)) return 1;
+            if (run_conv(net, n1, {.in = net->dmid.p, .out = net->dout[u].p, .N = N, .H = hh, .W = ww, .relu = 1, .in_gs = (long long)N * hh * ww * cmid, .roi = r_out}, st)) return 1;
+            prev = net->dout[u].p;
             prev_gs = (long long)N * hh * ww * oc[u];
         }
         HeadParams hps[8];
@@ -1021,13 +941,12 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             const int di = net->dense_idx[k];
             const size_t tk = (size_t)net->trunk_of[k];  // the decoder whose features this head reads
             const DecoderCfg& d = net->dec[di];
-            if (macs) *macs += (double)N * H * W * (64.0 * 96 + 96.0 * d.out_ch);
             const bool want = io->out && io->out[di];
             const bool wantl = io->logits && io->logits[di];
-            if (dry || !(want || wantl)) continue;
+            if (!(want || wantl)) continue;
             HeadParams hp;
             memset(&hp, 0, sizeof(hp));
-            hp.feat = feat_planar ? net->psum.b.p + tk * net->psum.gs() : net->dout[3].p + tk * (size_t)N * H * W * 64;  // (planar: the last level's output lives in its sum buffer)
+            hp.feat = feat_planar ? net->dec_sum[3].b.p + tk * net->dec_sum[3].gs() : net->dout[3].p + tk * (size_t)N * H * W * 64;  // (planar: the last level's output lives in its sum buffer)
             hp.feat_planar = feat_planar ? 1 : 0;
             hp.pl_byp = cerb_planar_blocks(H);
             hp.pl_bxp = cerb_planar_blocks(W);
@@ -1047,14 +966,10 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             const double head_px = hp.roi ? (double)out_h * (((hp.crop_x0 + out_w + 15) / 16 - hp.crop_x0 / 16) * 16.0) : (double)H * W;
             const double fl = 2.0 * N * head_px * (64.0 * 96 + 96.0 * d.out_ch);
             if (net->head_algo == 0) {  // one launch per head (round-1 kernel, kept for A/B: cerb_net_set_head_algo)
-                if (prof_begin(net, "head." + d.name, "head", fl, st)) return 1;
-                HIP_OK(cerb_launch_head(hp, st));
-                if (prof_end(net, st)) return 1;
+                PROF("head." + d.name, "head", fl, HIP_OK(cerb_launch_head(hp, st)));
             } else {
                 if (n_hp == 8) {  // a grouped launch carries at most 8 heads: more dense decoders go out in chunks of 8
-                    if (prof_begin(net, "heads", "head_group", head_flops, st)) return 1;
-                    HIP_OK(cerb_launch_head_group(hps, n_hp, st, net->head_algo == 1 ? 1 : 0));
-                    if (prof_end(net, st)) return 1;
+                    PROF("heads", "head_group", head_flops, HIP_OK(cerb_launch_head_group(hps, n_hp, st, net->head_algo == 1 ? 1 : 0)));
                     n_hp = 0;
                     head_flops = 0.0;
                 }
@@ -1063,12 +978,10 @@ static int forward_impl(cerb_net* net, const cerb_forward_io* io, hipStream_t st
             }
         }
         if (n_hp > 0) {  // all dense heads of the batch in ONE grouped launch (models/utils/net_layers.py:31-38 x5)
-            if (prof_begin(net, "heads", "head_group", head_flops, st)) return 1;
-            HIP_OK(cerb_launch_head_group(hps, n_hp, st, net->head_algo == 1 ? 1 : 0));
-            if (prof_end(net, st)) return 1;
+            PROF("heads", "head_group", head_flops, HIP_OK(cerb_launch_head_group(hps, n_hp, st, net->head_algo == 1 ? 1 : 0)));
         }
     }
-    if (!dry && io->feats) {
+    if (io->feats) {
         const float* src[6] = {net->x0.p, net->x[1].p, net->x[2].p, net->x[3].p, net->cm.p, net->x[4].p};
         const size_t nb[6] = {(size_t)N * H * W * 64, (size_t)N * hs[1] * ws[1] * 64, (size_t)N * hs[2] * ws[2] * 128,
                               (size_t)N * hs[3] * ws[3] * 256, (size_t)N * hs[4] * ws[4] * 256, (size_t)N * hs[4] * ws[4] * 512};
@@ -1117,8 +1030,7 @@ extern "C" int cerb_net_update_params(cerb_net* net, int count, const char* cons
     // every parameter tensor into its slot(s) in ONE launch (round 3: one hipMemcpyAsync per tensor, ~470 per optimiser step)
     HIP_OK(cerb_launch_copy_multi((int)cd.size(), cd.data(), cs.data(), cn.data(), &net->copy_tab, &net->copy_tab_bytes, &net->copy_tab_host, st));
     HIP_OK(cerb_launch_pack_stem(net->stem_raw, net->stem_w, st));
-    // every conv's re-layouts / filter transforms as jobs of ONE launch (pack_kernels.hip: pack_multi_kernel); CERB_PACK_PER_CONV=1: round 4's launches
-    static const bool per_conv = cerb_dev_getenv("CERB_PACK_PER_CONV") != nullptr;
+    // every conv's re-layouts / filter transforms as jobs of ONE launch (pack_kernels.hip: pack_multi_kernel)
     std::vector<PackJob> jobs;
     auto job = [&](const float* w, float* out, long long total, int cout, int cin, int kind, int a, int b) { jobs.push_back(PackJob{w, out, total, cout, cin, kind, a, b, 0}); };
     for (auto& kv : net->conv) {
@@ -1128,26 +1040,14 @@ extern "C" int cerb_net_update_params(cerb_net* net, int count, const char* cons
         if (pc.wino_dgrad && !pc.wino_dgrad_used) pc.wino_dgrad_stale = true;
         const size_t nw = (size_t)pc.cout * pc.cin * pc.ks * pc.ks, nu = (size_t)pc.cout * pc.cin * 16, nu4 = (size_t)pc.cout * pc.cin * 36;
         for (int g = 0; g < pc.groups; ++g) {
-            if (per_conv) {
-                HIP_OK(cerb_launch_pack_conv(rawd + g * nw, pc.w + g * nw, pc.cout, pc.cin, pc.ks, cerb_conv_chunk(pc.ks, pc.stride), st));
-                if (pc.wino && pc.wino_used) HIP_OK(cerb_launch_pack_wino(rawd + g * nw, pc.wino + g * nu, pc.cout, pc.cin, 0, st));
-                if (pc.wino_dgrad && pc.wino_dgrad_used) HIP_OK(cerb_launch_pack_wino(rawd + g * nw, pc.wino_dgrad + g * nu, pc.cin, pc.cout, 1, st));
-                continue;
-            }
             job(rawd + g * nw, pc.w + g * nw, (long long)nw, pc.cout, pc.cin, 0, pc.ks * pc.ks, cerb_conv_chunk(pc.ks, pc.stride));
             if (pc.wino && pc.wino_used) job(rawd + g * nw, pc.wino + g * nu, (long long)nu, pc.cout, pc.cin, 1, 0, 0);
             if (pc.wino_dgrad && pc.wino_dgrad_used) job(rawd + g * nw, pc.wino_dgrad + g * nu, (long long)nu, pc.cin, pc.cout, 1, 1, 0);
         }
         for (int l = 0; l < 2; ++l)  // the F(4x4) layouts in use
             for (int dg = 0; dg < 2; ++dg)
-                if (pc.wino4_t[l][dg]) {
-                    if (per_conv) {
-                        HIP_OK(cerb_launch_pack_wino4(rawd, pc.wino4_t[l][dg], dg ? pc.cin : pc.cout, dg ? pc.cout : pc.cin, dg, l, pc.groups, st));
-                        continue;
-                    }
-                    for (int g = 0; g < pc.groups; ++g)
-                        job(rawd + g * nw, pc.wino4_t[l][dg] + g * nu4, (long long)nu4, dg ? pc.cin : pc.cout, dg ? pc.cout : pc.cin, 2, dg, l);
-                }
+                for (int g = 0; pc.wino4_t[l][dg] && g < pc.groups; ++g)
+                    job(rawd + g * nw, pc.wino4_t[l][dg] + g * nu4, (long long)nu4, dg ? pc.cin : pc.cout, dg ? pc.cout : pc.cin, 2, dg, l);
     }
     if (!jobs.empty()) HIP_OK(cerb_launch_pack_multi(jobs.data(), (int)jobs.size(), &net->pack_tab, &net->pack_tab_bytes, &net->pack_tab_host, st));
     return 0;
@@ -1165,16 +1065,23 @@ extern "C" int cerb_net_forward(cerb_net* net, const cerb_forward_io* io, void* 
     if (!io->tiles && !io->tiles_f32) return fail("cerb_net_forward: null tiles pointer (neither tiles nor tiles_f32)");
     if (!net->fold_bn) return fail("cerb_net_forward: the network was packed for training (cerb_net_set_fold_bn(net, 0)); use cerb_net_forward_train");
     net->prof_n = 0;
-    return forward_impl(net, io, (hipStream_t)hip_stream, nullptr);
+    return forward_impl(net, io, (hipStream_t)hip_stream);
 }
 
 extern "C" double cerb_net_flops(const cerb_net* net, int n, int h, int w) {
     if (!net || !net->finalized) return -1.0;
-    cerb_forward_io io;
-    memset(&io, 0, sizeof(io));
-    io.n = n; io.h = h; io.w = w;
-    double macs = 0.0;
-    if (forward_impl(const_cast<cerb_net*>(net), &io, nullptr, &macs)) return -1.0;
+    if (n <= 0 || h <= 0 || w <= 0 || (h % 16) || (w % 16)) return -1.0;
+    // the multiply-accumulates of the whole network, heads a caller does not ask for included: the stem, every packed convolution at its stage's
+    // map size ("backbone.layer<L>..." writes the map of stage L, "dec.<u>..." that of decoder level u, conv_map the coarsest), Patch-Class, the heads
+    double macs = (double)n * h * w * 64.0 * 147.0;
+    for (const auto& kv : net->conv) {
+        const PackedConv& c = kv.second;
+        int k = 0;
+        const int shift = sscanf(kv.first.c_str(), "backbone.layer%d.", &k) == 1 ? k : sscanf(kv.first.c_str(), "dec.%d.", &k) == 1 ? 3 - k : 4;
+        macs += (double)c.groups * n * (h >> shift) * (w >> shift) * (double)c.cout * c.cin * c.ks * c.ks;
+    }
+    if (net->pc_idx >= 0) macs += (double)n * (512.0 * 256 + 256.0 * net->dec[net->pc_idx].out_ch);
+    for (int di : net->dense_idx) macs += (double)n * h * w * (64.0 * 96 + 96.0 * net->dec[di].out_ch);
     return 2.0 * macs;
 }
 

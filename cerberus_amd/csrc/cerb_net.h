@@ -1,6 +1,7 @@
 // Internal header of the C-ABI implementation: what cerb_api.hip (weight intake, packing, the inference forward) and cerb_train.hip (train-mode
 // forward, the backward tape, optimiser entry points) share -- the launcher prototypes of the kernel translation units, the handle (struct
-// cerb_net) and the host helpers both schedules call.  Not part of the boundary: include/cerberus_hip.h is.
+// cerb_net), the arguments of one convolution (ConvCall) and the host helpers both schedules call; which kernel a convolution takes is conv_plan.h's
+// rule.  Not part of the boundary: include/cerberus_hip.h is.
 #ifndef CERB_NET_H
 #define CERB_NET_H
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 
 #include "../../include/cerberus_hip.h"
 #include "cerb_common.h"
+#include "conv_plan.h"
 
 // launchers implemented in the kernel translation units
 hipError_t cerb_launch_conv(const ConvParams& p, int ks, int stride, int mode, hipStream_t st);
@@ -294,13 +296,11 @@ struct cerb_net {
     std::map<std::string, std::vector<std::string>> bn_keys;   // conv / bn name -> state-dict prefixes of its BatchNorm, one per group
     // workspace
     DevBuf x0, pool, x[5], ta, tb, cm, dmid, dsum, dout[4];
-    PlanarBuf psum, pmid, pout;  // the last decoder level's private tensors in the tile-planar layout (conv_wino4p.hip), cerb_net_set_planar; psum also
-                                 // receives the level's OUTPUT (it is dead once the first conv has read it): pout / pout2 are never allocated any more
-    int planar_level = 3;           // set by the decoder loop around a planar level's run_conv calls: the level (names the kernel symbol and the profile family);
-                                    // 4 = an encoder stage (conv_wino4_enc<...>)
-    PlanarBuf psum2, pmid2, pout2;  // the same for the level below it (64 channels at half the resolution) when its maps are large enough
-    PlanarBuf psum1, pmid1, pout1, psum0, pmid0, pout0;  // ... and for the quarter- and eighth-resolution levels (128 / 256 input channels) where those run
-                                                         // tile-planar; their output has fewer planes than their entry sum, so it has a buffer of its own
+    // The planar decoder levels' private tensors in the tile-planar layout (conv_wino4p.hip), cerb_net_set_planar, by level: the entry sum, the first
+    // conv's output, the second's.  On the two last levels (64 -> 64 channels) dec_sum also receives the level's OUTPUT (it is dead once the first conv
+    // has read it), so dec_out[2] and dec_out[3] are never allocated; the quarter- and eighth-resolution levels (128 / 256 input channels) have fewer
+    // output planes than their entry sum, so their output has a buffer of its own.
+    PlanarBuf dec_sum[4], dec_mid[4], dec_out[4];
     // The encoder's residual stages that run tile-planar (cerb_api.hip: encoder_stage_is_planar), per stage: enc_a = the block's identity and, written over
     // it, the block's output; enc_b = the first convolution's output.
     PlanarBuf enc_a[4], enc_b[4];
@@ -316,10 +316,6 @@ struct cerb_net {
     std::vector<ProfRec> prof;
     size_t prof_n = 0;
     bool prof_open = false;  // a record is open (prof_begin without its prof_end yet)
-    // training forward: where the NEXT run_conv may leave BatchNorm statistics partials (ConvParams::bn_part); run_conv clears the request and
-    // reports in conv_bn_bpg how many blocks per group it wrote (0: this convolution's kernel does not produce them)
-    double* conv_bn_part = nullptr;
-    int conv_bn_bpg = 0;
     // training backward: the weight gradients of the 3x3 / 1x1 convolutions run on a side stream of the handle's own (forked from the caller's stream when the
     // layer's output gradient is final, joined at the end of cerb_net_train_grads): matrix-core work that overlaps the BatchNorm backward passes (HBM-bound, no
     // LDS) and fills the last-round tails of the data-gradient launches.  Same kernels, same arithmetic.  CERB_WGRAD_SIDE=0 / profiling: everything on one stream.
@@ -335,10 +331,10 @@ struct cerb_net {
         for (void* p : dev_allocs) (void)hipFree(p);
         if (copy_tab) (void)hipFree(copy_tab);
         if (pack_tab) (void)hipFree(pack_tab);
-        x0.release(); pool.release(); ta.release(); tb.release(); cm.release(); dmid.release(); dsum.release(); psum.release(); pmid.release(); pout.release(); psum2.release(); pmid2.release(); pout2.release(); psum1.release(); pmid1.release(); pout1.release(); psum0.release(); pmid0.release(); pout0.release();
+        x0.release(); pool.release(); ta.release(); tb.release(); cm.release(); dmid.release(); dsum.release();
         t_mean.release(); t_rstd.release(); t_ws.release(); t_hid.release(); t_gap.release(); t_pc1.release(); t_idn.release(); t_dil.release();
-        for (auto& b : enc_a) b.release();
-        for (auto& b : enc_b) b.release();
+        for (PlanarBuf* bufs : {dec_sum, dec_mid, dec_out, enc_a, enc_b})
+            for (int i = 0; i < 4; ++i) bufs[i].release();
         for (auto& b : tape) b.release();
         for (auto& b : x) b.release();
         for (auto& b : dout) b.release();
@@ -359,10 +355,25 @@ void cerb_host_pack_wino(const float* w, int cout, int cin, std::vector<float>* 
 void cerb_host_pack_wino4(const float* w, int cout, int cin, int layout, std::vector<float>* out);         // F(4x4,3x3) transform; layout 0 = conv_wino4 / 4p, 1 = conv_wino4b
 int prof_begin(cerb_net* net, const std::string& name, const std::string& kernel, double flops, hipStream_t st);  // per-launch records (cerb_net_profile_*)
 int prof_end(cerb_net* net, hipStream_t st);
+// one per-launch profile record (cerb_net_profile_*) around a launch of the families run_conv does not cover, so that a
+// profiled step attributes ALL of its device time; `work` = FLOPs of a matrix-core family, algorithmic bytes of an HBM-bound one
+#define PROF(nm, kern, work, stmt) do { if (prof_begin(net, (nm), (kern), (work), st)) return 1; stmt; if (prof_end(net, st)) return 1; } while (0)
 int train_wino2_fresh(cerb_net* net, const std::string& name, PackedConv& cm, int dgrad, hipStream_t st);
 int train_wino4_slot(cerb_net* net, const std::string& name, PackedConv& cm, int w4b, int dgrad, hipStream_t st, float** out);
-// one convolution of the schedule by its packed name (algorithm by cerb_net_set_conv_algo and the layer's geometry); planar_out_gs > 0: in / out are tile-planar
-// (a stride-2 convolution: `out` only -- conv_igemm.hip's planar epilogue)
-int run_conv(cerb_net* net, const std::string& name, const float* in, const float* prev, const float* resid, float* out, int N, int H, int W, int relu, int mode,
-             long long in_gs, long long prev_gs, hipStream_t st, double* macs, const int* roi = nullptr, long long planar_out_gs = 0);
+// One convolution of the schedule by its packed name; the kernel by conv_plan.h's rule from cerb_net_set_conv_algo and the layer's geometry.
+struct ConvCall {
+    const float* in = nullptr;     // [groups][N][H][W][cin] (in_gs between groups; 0: one input shared by every group)
+    const float* prev = nullptr;   // mode 1: the coarser map that is upsampled and added on the load (prev_gs between groups)
+    const float* resid = nullptr;  // added before the ReLU
+    float* out = nullptr;
+    int N = 0, H = 0, W = 0;       // input geometry
+    int relu = 0, mode = 0;
+    long long in_gs = 0, prev_gs = 0;
+    const int* roi = nullptr;      // {y0, y1, x0, x1} of the output the caller needs (Winograd kernels only), or null
+    long long planar_out_gs = 0;   // > 0: in / out are tile-planar (a stride-2 convolution: `out` only -- conv_igemm.hip's planar epilogue), elements between groups
+    int site = -1;                 // of a tile-planar launch: the decoder level 0..3 or kSiteEncoder
+    double* bn_part = nullptr;     // training forward: where the kernel may leave BatchNorm statistics partials (ConvParams::bn_part) ...
+    int* bn_bpg = nullptr;         // ... and where run_conv reports how many blocks per group it wrote (0: this launch did not produce them)
+};
+int run_conv(cerb_net* net, const std::string& name, const ConvCall& a, hipStream_t st);
 #endif  // CERB_NET_H

@@ -55,7 +55,6 @@ extern "C" int cerb_net_forward_train(cerb_net* net, const cerb_train_io* io, vo
         for (int u = 0; u < 4; ++u)
             if (net->dout[u].ensure(D * (size_t)N * hs[3 - u] * ws[3 - u] * oc[u] * 4, guard)) return fail_alloc();
     }
-    const int saved_algo = net->conv_algo;
     // ---- encoder: conv -> BN(batch) -> ReLU -----------------------------------------------------------------------------------
     {
         StemParams sp;
@@ -78,22 +77,22 @@ extern "C" int cerb_net_forward_train(cerb_net* net, const cerb_train_io* io, vo
             float* t1 = net->ta.p;
             float* outb = ((kLayers[li] - 1 - b) % 2 == 0) ? net->x[li + 1].p : net->tb.p;
             const float* idt = cur;
-            if (run_conv(net, p + ".conv1", cur, nullptr, nullptr, t1, N, hin, win, 0, 0, 0, 0, st, nullptr)) return 1;
+            if (run_conv(net, p + ".conv1", {.in = cur, .out = t1, .N = N, .H = hin, .W = win}, st)) return 1;
             if (bn_train(net, p + ".conv1", t1, nullptr, 0, rows_out, 1, st)) return 1;
             if (stride != 1 || inpl != planes) {
                 // the identity branch needs its own buffer here: in layer1.0 there is none, later the pool buffer is free but smaller maps fit
                 if (net->t_idn.ensure((size_t)rows_out * planes * 4, guard)) return fail_alloc();
-                if (run_conv(net, p + ".downsample", cur, nullptr, nullptr, net->t_idn.p, N, hin, win, 0, 0, 0, 0, st, nullptr)) return 1;
+                if (run_conv(net, p + ".downsample", {.in = cur, .out = net->t_idn.p, .N = N, .H = hin, .W = win}, st)) return 1;
                 if (bn_train(net, p + ".downsample", net->t_idn.p, nullptr, 0, rows_out, 0, st)) return 1;
                 idt = net->t_idn.p;
             }
-            if (run_conv(net, p + ".conv2", t1, nullptr, nullptr, outb, N, hs[li + 1], ws[li + 1], 0, 0, 0, 0, st, nullptr)) return 1;
+            if (run_conv(net, p + ".conv2", {.in = t1, .out = outb, .N = N, .H = hs[li + 1], .W = ws[li + 1]}, st)) return 1;
             if (bn_train(net, p + ".conv2", outb, idt, 0, rows_out, 1, st)) return 1;  // relu(bn2(conv2) + identity)
             cur = outb;
             inpl = planes;
         }
     }
-    if (run_conv(net, "conv_map", net->x[4].p, nullptr, nullptr, net->cm.p, N, hs[4], ws[4], 0, 0, 0, 0, st, nullptr)) return 1;
+    if (run_conv(net, "conv_map", {.in = net->x[4].p, .out = net->cm.p, .N = N, .H = hs[4], .W = ws[4]}, st)) return 1;
     // ---- Patch-Class: crop -> GAP -> BN -> ReLU -> dropout -> 1x1 -> BN -> ReLU -> 1x1 (models/net_desc.py:64-76,169-180) -----------------
     if (net->pc_idx >= 0 && io->logits[net->pc_idx]) {
         const int ocp = net->dec[net->pc_idx].out_ch;
@@ -128,9 +127,9 @@ extern "C" int cerb_net_forward_train(cerb_net* net, const cerb_train_io* io, vo
             const int cmid = net->conv[n0].cout, cin0 = net->conv[n0].cin;
             const long long rows = (long long)N * hh * ww;
             HIP_OK(cerb_launch_upsample2_add(skips[u], prev, net->dsum.p, (int)D, N, hh, ww, cin0, prev_gs, nullptr, st));
-            if (run_conv(net, n0, net->dsum.p, nullptr, nullptr, net->dmid.p, N, hh, ww, 0, 0, rows * cin0, 0, st, nullptr)) return 1;
+            if (run_conv(net, n0, {.in = net->dsum.p, .out = net->dmid.p, .N = N, .H = hh, .W = ww, .in_gs = rows * cin0}, st)) return 1;
             if (bn_train(net, n0, net->dmid.p, nullptr, rows * cmid, rows, 1, st)) return 1;
-            if (run_conv(net, n1, net->dmid.p, nullptr, nullptr, net->dout[u].p, N, hh, ww, 0, 0, rows * cmid, 0, st, nullptr)) return 1;
+            if (run_conv(net, n1, {.in = net->dmid.p, .out = net->dout[u].p, .N = N, .H = hh, .W = ww, .in_gs = rows * cmid}, st)) return 1;
             if (bn_train(net, n1, net->dout[u].p, nullptr, rows * oc[u], rows, 1, st)) return 1;
             prev = net->dout[u].p;
             prev_gs = rows * oc[u];
@@ -145,7 +144,6 @@ extern "C" int cerb_net_forward_train(cerb_net* net, const cerb_train_io* io, vo
             HIP_OK(cerb_launch_pointwise(net->t_hid.p, net->head_rw2[k], net->head_rb2[k], io->logits[di], rows, 96, net->dec[di].out_ch, nullptr, st));
         }
     }
-    net->conv_algo = saved_algo;
     return 0;
 }
 
@@ -232,7 +230,6 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
         net->grads[key] = std::make_pair(p, (long long)n);
         return p;
     };
-    const int saved_algo = net->conv_algo;
     // side stream of the weight gradients (see cerb_net::side): off under per-launch profiling (the records time one stream) and with CERB_WGRAD_SIDE=0
     bool side_wgrad = !net->profiling;
     {
@@ -259,18 +256,16 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
         // BatchNorm statistics partials from the convolution's own output stage (3x3 stride-1 layers on the F(4x4) kernels): one (sum, sum of
         // squares) per 16 x 16 block, group and channel, in a buffer of the tape arena that the bn() behind this conv finalises
         double* part = nullptr;
-        // only where run_conv will pick an F(4x4) kernel (its own rule: maps of at least 16 x 16 pixels under the default algorithm) -- the F(2x2) and
-        // direct kernels have no statistics stage, a buffer taken for them would only be arena churn
-        const long long map_px = (long long)ho * wo;
-        const bool f4 = net->conv_algo == 5 || net->conv_algo == 7 || (net->conv_algo == 6 && map_px >= 256);
-        if (c.ks == 3 && c.stride == 1 && f4 && c.wino && !bn_stats_pass) {
+        // only where the kernel run_conv takes has a statistics stage (conv_plan.h: the F(4x4) kernels) -- a buffer taken for the F(2x2) and direct
+        // kernels would only be arena churn
+        int bpg = 0;
+        if (!bn_stats_pass && conv_has_bn_stats(conv_plan({net->conv_algo, c.ks, c.stride, c.cin, c.cout, ho, wo, c.wino != nullptr, 0, false, true}))) {
             const size_t nblk = (size_t)n_ * ((ho + 15) / 16) * ((wo + 15) / 16);
             part = (double*)take((size_t)c.groups * nblk * c.cout * 2 * 2, false);
             if (!part) return -1;
-            net->conv_bn_part = part;
         }
-        if (!val[o] || run_conv(net, name, val[a], nullptr, nullptr, val[o], n_, h_, w_, 0, 0, a_gs, 0, st, nullptr)) return -1;
-        if (part && net->conv_bn_bpg > 0) conv_stats[o] = std::make_pair(part, net->conv_bn_bpg);
+        if (!val[o] || run_conv(net, name, {.in = val[a], .out = val[o], .N = n_, .H = h_, .W = w_, .in_gs = a_gs, .bn_part = part, .bn_bpg = &bpg}, st)) return -1;
+        if (bpg > 0) conv_stats[o] = std::make_pair(part, bpg);
         TapeOp op;
         op.type = 1; op.name = name; op.a = a; op.o = o; op.N = n_; op.H = h_; op.W = w_; op.Cin = c.cin; op.Cout = c.cout; op.ks = c.ks; op.stride = c.stride;
         op.G = c.groups; op.a_gs = a_gs;
@@ -340,10 +335,7 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
         tape.push_back(op);
         return z;
     };
-#define TCHK(x) do { if ((x) < 0) { net->conv_algo = saved_algo; return fail(std::string("cerb_net_train_grads: ") + #x + " failed"); } } while (0)
-// one per-launch profile record (cerb_net_profile_*) around a launch of the families that run_conv / bn / wgrad do not cover themselves, so that a
-// profiled step attributes ALL of its device time; `work` = FLOPs of a matrix-core family, algorithmic bytes of an HBM-bound one
-#define PROF(nm, kern, work, stmt) do { if (prof_begin(net, (nm), (kern), (work), st)) return 1; stmt; if (prof_end(net, st)) return 1; } while (0)
+#define TCHK(x) do { if ((x) < 0) return fail(std::string("cerb_net_train_grads: ") + #x + " failed"); } while (0)
 #define PROFN(nm, kern, work, stmt) do { if (prof_begin(net, (nm), (kern), (work), st)) return -1; stmt; if (prof_end(net, st)) return -1; } while (0)
     const int t_stem = newT((size_t)N * H * W * 64);
     {
@@ -363,7 +355,7 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
     const bool pool_scan = cerb_dev_getenv("CERB_MAXPOOL_SCAN") != nullptr;  // read once per step
     const int pool_idx = pool_scan ? -1 : newT(((size_t)N * hs[1] * ws[1] * 64 + 3) / 4);
     if (pool_idx >= 0) {
-        if (!val[pool_idx]) { net->conv_algo = saved_algo; return fail_alloc(); }
+        if (!val[pool_idx]) return fail_alloc();
         PROF("maxpool", "maxpool3x3s2", (double)N * H * W * 64 * 4.0 * 1.25 + (double)N * hs[1] * ws[1] * 64.0,
              HIP_OK(cerb_launch_maxpool_idx(val[x0], val[pool], reinterpret_cast<unsigned*>(val[pool_idx]), N, H, W, 64, st)));
     } else {
@@ -613,37 +605,21 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
                 }
                 const PackedConv& pcv = net->conv[op.name];
                 bool dx_done = false;
-                if (pcv.wino_dgrad && net->conv_algo && (op.stride == 1 || (op.H % 2 == 0 && op.W % 2 == 0))) {
-                    // data gradient on the forward Winograd kernel: in = dy, weights rotated + transposed, the gradient already held by the
-                    // input (other consumers) rides in as the residual and is written back in place
+                // The data gradient of a 3x3 layer is the stride-1 convolution of dy (stride 2: spread onto the even positions) with the rotated, transposed
+                // weights: the forward kernels by the forward rule (conv_plan.h), asked with the channel roles swapped.  wino_dgrad exists for ks == 3,
+                // Cin % 64 == 0, Cout % 32 == 0 (make_conv), which is what the F(4x4) kernels need of their output / contraction channels here.
+                const ConvLayer dl{net->conv_algo, op.ks, 1, op.Cout, op.Cin, op.H, op.W, pcv.wino_dgrad != nullptr, 0, false, true};
+                const ConvKernel dk = conv_plan(dl);
+                if (dk != CONV_IGEMM && (op.stride == 1 || (op.H % 2 == 0 && op.W % 2 == 0))) {
+                    // in = dy, the gradient already held by the input (other consumers) rides in as the residual and is written back in place
                     const long long in_n = (long long)op.N * op.H * op.W * op.Cin;
                     const bool fresh = !grd[op.a] && cnt[op.a] == (size_t)op.G * in_n && (op.G == 1 || op.a_gs == in_n);  // first writer: no residual, no zero fill
                     if (fresh && !(grd[op.a] = take(cnt[op.a], false))) return fail_alloc();
                     float* dx = G_(op.a);
-                    const long long map_px = (long long)op.H * op.W;
-                    const bool d_w4 = saved_algo == 5 || saved_algo == 7 || (saved_algo == 6 && map_px >= 256);
-                    static const long long d_w4b_max_px = [] {  // developer A/B only, as in run_conv
-                        const char* e = cerb_dev_getenv("CERB_W4B_MAX_PX");
-                        return e ? atoll(e) : 4096ll;
-                    }();
-                    const bool d_w4b = (saved_algo == 7 || (saved_algo == 6 && map_px <= d_w4b_max_px)) && op.Cout % 64 == 0;
-                    const bool d_f4 = d_w4 && op.Cout % 16 == 0 && op.Cin % 64 == 0;
-                    // the data gradient as its own family: the forward Winograd kernels on rotated weights (+ the stride-2 dilation pass)
-                    ConvParams q;  // the geometry conv_wino4b's launcher decides its item form by
-                    memset(&q, 0, sizeof(q));
-                    q.N = op.N; q.H = q.Ho = op.H; q.W = q.Wo = op.W; q.Cin = op.Cout; q.Cout = op.Cin; q.pk_off = net->packed_items ? 0 : 1;
-                    const bool d_pk = d_f4 && d_w4b && cerb_wino4b_packed(q);
-                    if (prof_begin(net, op.name + ".dgrad", std::string("dgrad:") + (d_f4 ? (d_w4b ? (d_pk ? "conv_wino4b<f4x4,16t>" : "conv_wino4b<f4x4,16x16>") : "conv_wino4<f4x4,16x16x2>") : "conv_wino<f2x2,8x16>"),
-                                   2.0 * op.G * op.N * op.H * op.W * (double)op.Cin * op.Cout * 9.0, st)) return 1;
-                    if (op.stride == 2) {  // y = 2 yo - 1 + ky  <=>  dx = conv_s1(D, W'), D[2 yo][2 xo] = dy[yo][xo], zero elsewhere
-                        const long long dn = (long long)op.G * op.N * op.H * op.W * op.Cout;
-                        if (net->t_dil.ensure((size_t)dn * 4, cerb_conv_guard_bytes(W))) return fail_alloc();
-                        HIP_OK(cerb_launch_dilate2(go, net->t_dil.p, (long long)op.G * op.N, op.H, op.W, op.Cout, st));
-                        go = net->t_dil.p;
-                    }
+                    const bool d_w4b = dk == CONV_WINO4B, d_f4 = d_w4b || dk == CONV_WINO4;  // (else F(2x2))
                     ConvParams p;
                     memset(&p, 0, sizeof(p));
-                    p.in = go; p.wpack = pcv.wino_dgrad; p.bias = net->zero_bias; p.resid = fresh ? nullptr : dx; p.out = dx;
+                    p.wpack = pcv.wino_dgrad; p.bias = net->zero_bias; p.resid = fresh ? nullptr : dx; p.out = dx;
                     p.N = op.N; p.H = op.H; p.W = op.W; p.Cin = op.Cout; p.Cout = op.Cin; p.Ho = op.H; p.Wo = op.W; p.relu = 0; p.groups = op.G;
                     p.in_gs = (long long)op.N * op.H * op.W * op.Cout;
                     p.w_gs = (long long)op.Cout * op.Cin * 16;
@@ -652,10 +628,19 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
                     p.out_gs = op.a_gs;
                     if (op.G == 1) p.resid_gs = p.out_gs = 0;
                     p.pk_off = net->packed_items ? 0 : 1;
-                    // the same per-geometry choice as the forward convolutions (run_conv): F(4x4,3x3) for maps of 16 x 16 and more
+                    // the data gradient as its own family: the forward kernel's name behind "dgrad:" (+ the stride-2 dilation pass)
+                    if (prof_begin(net, op.name + ".dgrad", "dgrad:" + conv_family(dk, dl, false, d_w4b && cerb_wino4b_packed(p), -1),
+                                   2.0 * op.G * op.N * op.H * op.W * (double)op.Cin * op.Cout * 9.0, st)) return 1;
+                    if (op.stride == 2) {  // y = 2 yo - 1 + ky  <=>  dx = conv_s1(D, W'), D[2 yo][2 xo] = dy[yo][xo], zero elsewhere
+                        const long long dn = (long long)op.G * op.N * op.H * op.W * op.Cout;
+                        if (net->t_dil.ensure((size_t)dn * 4, cerb_conv_guard_bytes(W))) return fail_alloc();
+                        HIP_OK(cerb_launch_dilate2(go, net->t_dil.p, (long long)op.G * op.N, op.H, op.W, op.Cout, st));
+                        go = net->t_dil.p;
+                    }
+                    p.in = go;
                     if (d_f4) {
                         float* w4 = nullptr;
-                        if (train_wino4_slot(net, op.name, net->conv[op.name], d_w4b ? 1 : 0, 1, st, &w4)) return 1;
+                        if (train_wino4_slot(net, op.name, net->conv[op.name], d_w4b, 1, st, &w4)) return 1;
                         p.wpack = w4;
                         p.w_gs = (long long)op.Cout * op.Cin * 36;
                         // Is this data gradient the ONLY writer of the gradient behind a train-mode BatchNorm + ReLU (no residual)?  Then its output stage leaves
@@ -948,9 +933,7 @@ extern "C" int cerb_net_train_grads(cerb_net* net, const cerb_train_step_io* io,
         }
     }
 #undef TCHK
-#undef PROF
 #undef PROFN
-    net->conv_algo = saved_algo;
     if (side_used) {  // the caller's stream continues (optimiser, all-reduce, the next step's tape) once the side stream's weight gradients are complete
         HIP_OK(hipEventRecord(net->ev_join, net->side));
         HIP_OK(hipStreamWaitEvent(st, net->ev_join, 0));

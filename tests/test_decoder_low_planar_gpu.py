@@ -16,7 +16,7 @@ from conftest import dev_switches
 
 pytestmark = pytest.mark.gpu
 
-LOW_CONV = "conv_wino4_planar<"      # profile families of the two lowest levels' convolutions (cerb_api.hip: kPlanarFamily)
+LOW_CONV = "conv_wino4_planar<"      # profile families of the two lowest levels' convolutions (conv_plan.h: kPlanarFamily)
 LOW_ENTRY = "upsample2_add_planar<"  # ... and of their entry passes
 PLANAR_LOW_LEVELS = 2                # how many of the two lowest levels ship tile-planar (cerb_api.hip: kPlanarLowest = 0)
 _models = {}
